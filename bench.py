@@ -19,7 +19,11 @@ atomics; forward and reverse complement). FASTQ parsing and the index build are 
 Rounds 1 and 2 timed a narrower region as `value` (reads resident in HBM, one batch replayed, coverage left in HBM): that
 figure is still on the line as `kernel_pipeline` — the two are NOT comparable.
 
-Extra keys (rank 0; the side legs run at N = 1 only unless noted):
+A plain run (no --full) does only what the headline needs: set-up, --warmup steps, ONE job of exactly --steps timed steps,
+the outputs (--dump-outputs DIR: the coverage arrays and read counters that job handed back, as DIR/<name>.npy in float64)
+and the result line (`value`, `ms_per_step`: that job). Everything below runs only with --full.
+
+Extra keys of --full (rank 0; the side legs run at N = 1 only unless noted):
   kernel_pipeline  reads resident in HBM (one byte per base), the same batch every step, coverage left in HBM
   sustained        the `value` loop for >= 1 s
   exchange_ms      (N > 1) the coverage exchange alone, timed between fences after the job
@@ -35,6 +39,7 @@ Extra keys (rank 0; the side legs run at N = 1 only unless noted):
   configs          (N = 1) BASELINE.json configs[2], configs[3] and (on a box with >= 280 GiB of host memory) configs[4] built at
                    full size: kernel-pipeline and packed-feed reads/s, their leading kernels' durations and roofline objects
   jobs             the timed job (exactly --steps steps) is run as often as it takes to add up to 1 s; `value` is the MEDIAN job
+                   (a plain run times one job unless --jobs says otherwise)
 """
 import argparse
 import json
@@ -487,6 +492,29 @@ def config_leg(which, n_reads, steps, device, stream):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, cov):
+    """What the timed path hands its caller (qm.coverage() after the job): the raw device totals of the three coverage
+    arrays, the grouped-count log (when it holds records) and the five read counters, as float64 (every count is a uint32 /
+    uint64 far below 2^53). An array that would take the files past 64 MB in all is replaced by a fixed, seeded sample of its elements."""
+    st = cov.stats
+    arrays = {"allele_sum": cov.raw_allele_sum, "per_base": cov.raw_per_base, "grouped": cov.raw_grouped,
+              "grouped_log": cov.raw_grouped_log,   # (records only for sites of more than 8 alleles: none at configs[1])
+              "read_stats": np.array([st.all_reads_count, st.skipped_reads_count, st.missing_kmer_reads_count,
+                                      st.no_extension_reads_count, st.exact_mapped_reads_count], dtype=np.uint64)}
+    share = DUMP_BUDGET_BYTES // (8 * len(arrays))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if a.size == 0:   # (an empty array is no output: not written)
+            continue
+        if a.size > share:
+            a = a[np.sort(np.random.default_rng(12345).choice(a.size, share, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -496,13 +524,19 @@ def main():
     ap.add_argument("--total-reads", type=int, default=0,
                     help="strong scaling: this many reads per step for the WHOLE job, split over the GPUs")
     ap.add_argument("--batches", type=int, default=N_BATCHES, help="distinct batches of reads cycled by the timed loop")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: the roofline leg, the side legs, the --configs legs, the CPU baseline "
+                         "and repeated timed jobs (default: set-up, warm-up, one timed job of --steps steps, the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed job returned (coverage arrays, read counters) as DIR/<name>.npy in float64")
     ap.add_argument("--jobs", type=int, default=0, help="the timed job (exactly --steps steps) is run this many times; value = the median job. "
-                                                        "0 (default): as many as it takes for the jobs to add up to 1 s of timed work (5 <= jobs <= 150)")
-    ap.add_argument("--configs", default="2,3,4", help="N = 1 side legs: BASELINE configs built at full size (configs[4] runs when the box has >= 280 GiB of host memory: ~6 minutes; "
+                                                        "0 (default): one job; with --full as many as it takes for the jobs to add up to 1 s "
+                                                        "of timed work (5 <= jobs <= 150)")
+    ap.add_argument("--configs", default="2,3,4", help="--full, N = 1 side legs: BASELINE configs built at full size (configs[4] runs when the box has >= 280 GiB of host memory: ~6 minutes; "
                                                        "GMX_BENCH_SKIP_C4=1 leaves it out)")
     ap.add_argument("--config-reads", type=int, default=1_000_000, help="reads per step of the --configs legs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip kernel_pipeline / sustained / cli_end_to_end / roofline leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip kernel_pipeline / sustained / cli_end_to_end / bgzf / configs legs")
     ap.add_argument("--cli-reads", type=int, default=4_000_000, help="reads in the FASTQ of the cli_end_to_end leg")
     ap.add_argument("--torch-exchange", action="store_true", help="N > 1: all-reduce through torch.distributed instead of the library")
     ap.add_argument("--planes", action="store_true",
@@ -536,7 +570,7 @@ def main():
     n = args.total_reads // world if strong else args.reads
     NB = max(1, args.batches)
     t0 = time.time()
-    threads = min(os.cpu_count() or 8, 64)
+    threads = min(effective_cores(), 64)   # (the cores this process may use: the hardware threads can be many times more)
     with ThreadPoolExecutor(max_workers=min(NB, max(1, threads // max(world, 1)))) as ex:
         # batch j of this rank: its own random stream (distinct reads in every batch and on every rank)
         raw = list(ex.map(lambda j: simulate_snp_reads_fast(ref, pos, alts, n_alts, n, READ_LEN, 1000 + 97 * j + rank), range(NB)))
@@ -614,29 +648,30 @@ def main():
             dt = float(tt.item())
         return dt, own, out
 
-    # ---- side legs first (the device has idled through the index build: they also bring its clocks up) ----
-    extras = world == 1 and not args.no_extras
+    # ---- --full: side legs first (the device has idled through the index build: they also bring its clocks up) ----
+    extras = args.full and world == 1 and not args.no_extras
     side = {}
     tm = None
-    d_reads = torch.from_numpy(reads.reshape(-1)).cuda()
-    d_offs = torch.from_numpy(offs.astype(np.int64)).cuda()
-    d_seeds = torch.from_numpy(np.asarray(seeds).astype(np.int64)).to(torch.int32).cuda()
+    if args.full:
+        d_reads = torch.from_numpy(reads.reshape(-1)).cuda()
+        d_offs = torch.from_numpy(offs.astype(np.int64)).cuda()
+        d_seeds = torch.from_numpy(np.asarray(seeds).astype(np.int64)).to(torch.int32).cuda()
 
-    def kernel_job(steps):  # rounds 1-2's region: reads resident in HBM, the same batch every step, coverage left in HBM
-        qm.reset(stream=stream)
-        for _ in range(steps):
-            qm.map_reads_device(d_reads, d_offs, d_seeds, n, stream=stream)
-        exchange_coverage()
+        def kernel_job(steps):  # rounds 1-2's region: reads resident in HBM, the same batch every step, coverage left in HBM
+            qm.reset(stream=stream)
+            for _ in range(steps):
+                qm.map_reads_device(d_reads, d_offs, d_seeds, n, stream=stream)
+            exchange_coverage()
 
-    # roofline leg: the dominant kernel bracketed by HIP events attached to its dispatch inside the library
-    kernel_job(10)
-    qm.enable_timing(True)
-    fence()
-    kernel_job(5)
-    fence()
-    tm = qm.timing()
-    qm.enable_timing(False)
-    q1 = qm.queue_counts() if rank == 0 else None
+        # roofline leg: the dominant kernel bracketed by HIP events attached to its dispatch inside the library
+        kernel_job(10)
+        qm.enable_timing(True)
+        fence()
+        kernel_job(5)
+        fence()
+        tm = qm.timing()
+        qm.enable_timing(False)
+        q1 = qm.queue_counts() if rank == 0 else None
     if extras:
         dtk, _, _ = timed(kernel_job, args.steps)
         side["kernel_pipeline"] = {"value": n * args.steps / dtk, "unit": "reads/s", "ms_per_step": dtk / args.steps * 1e3,
@@ -667,7 +702,10 @@ def main():
     # (round 6: `value` rests on >= 1 s of timed jobs — a K = 20 job takes 15 ms and five of them were all the headline stood on;
     #  every job is still EXACTLY K steps between its own fences, the count of jobs is what grows)
     runs = [timed(job, args.steps, args.warmup)]
-    n_jobs = args.jobs if args.jobs > 0 else int(min(150, max(5, -(-1.0 // max(runs[0][0], 1e-4)))))
+    if args.jobs > 0:
+        n_jobs = args.jobs
+    else:
+        n_jobs = int(min(150, max(5, -(-1.0 // max(runs[0][0], 1e-4))))) if args.full else 1
     if world > 1:  # (every rank must run the same number of jobs: rank 0's count)
         nj = torch.tensor([n_jobs], device="cuda")
         dist.broadcast(nj, 0)
@@ -687,10 +725,46 @@ def main():
         dte, _, _ = timed(exchange_coverage)   # the exchange alone (the block holds the job's totals: sums again, unused)
         exchange_ms = dte * 1e3
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, runs[-1][2])
+
     total_reads = n * world * args.steps
     value = total_reads / dt
     out = None
     if rank == 0:
+        h2d_per_read = (8 * ((READ_LEN + 31) // 32) if args.planes else READ_LEN / 4) + (4 if args.upload_seeds else 0)
+        h2d_gbs = h2d_per_read * value / world / 1e9
+        out = {
+            "metric": "150bp reads quasimapped/sec (whole node); bit-exact coverage",
+            "value": value, "unit": "reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong" if strong else "weak",
+            "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+            "value_is": "SURVEY §8(d) region: host buffers in (2-bit planes, page-locked) -> H2D -> kernels -> (N > 1: one exchange) "
+                        "-> D2H: coverage arrays final on the host; distinct reads every step",
+            "timed_region": "changed in round 3: rounds 1-2 timed the kernel pipeline only (reads resident in HBM, one batch replayed, "
+                            "coverage left in HBM; that figure is the key `kernel_pipeline`), and N > 1 jobs do ONE exchange at the "
+                            "end of the job, not one per step: values of different rounds are not comparable",
+            "config": {"workload": "configs[1]: M. tuberculosis scale, 4411532 bp random ref + 60000 SNP PRG, k=10, "
+                                   f"{n} x 150 bp reads per GPU per step, fwd+rc, {NB} distinct batches cycled, reads handed over as "
+                                   + ("2-bit planes" if args.planes else "a 2-bit stream (37.5 B per read)") + " in page-locked host memory"
+                                   + ("" if args.upload_seeds else ", per-read seeds read in place from page-locked host memory")
+                                   + "; no skip plane (the synthetic reads hold no N: gmx.h takes a null skip pointer as 'none skipped')",
+                       "reads_per_gpu": n, "read_len": READ_LEN, "kmer_size": KMER, "distinct_batches": NB,
+                       "h2d_bytes_per_read": h2d_per_read,
+                       "parallelism": f"reads sharded x{world} by global read index, index replicated, one RCCL all-reduce of the "
+                                      "coverage block per JOB (after the last step), then D2H",
+                       "exchange": exchange, "index_build_s": round(t_index, 2), "reads_generation_s": round(t_reads, 2),
+                       "index_bytes": int(ix.info.index_bytes)},
+            "h2d_rate_GBps": h2d_gbs,
+            "jobs": {"n": len(job_seconds), "total_seconds": float(sum(job_seconds)),
+                     "value_is": "the median job (each job: exactly `steps` steps between fences; "
+                                 + ("enough jobs for >= 1 s of timed work)" if args.full and args.jobs <= 0 else f"{len(job_seconds)} job(s))"),
+                     "min_value": total_reads / max(job_seconds), "max_value": total_reads / min(job_seconds),
+                     "p10_p90_values": [total_reads / float(np.percentile(job_seconds, 90)), total_reads / float(np.percentile(job_seconds, 10))],
+                     "first_values": [total_reads / x for x in job_seconds[:8]]},
+            "stats_job": st,
+        }
+    if rank == 0 and args.full:
         search_s = tm["search_ms"] / 1e3 / max(tm["search_launches"], 1)
         reads_per_launch = tm["reads"] / max(tm["search_launches"], 1)
         achieved = B_DESIGN_PER_READ * reads_per_launch / search_s / 1e9 if search_s > 0 else 0.0
@@ -699,8 +773,6 @@ def main():
         sq, sq_src = profile_json("sq_extend.json")
         sq = sq or {}
         traffic, traffic_src = measured_traffic("gmx_extend_kernel")
-        h2d_per_read = (8 * ((READ_LEN + 31) // 32) if args.planes else READ_LEN / 4) + (4 if args.upload_seeds else 0)
-        h2d_gbs = h2d_per_read * value / world / 1e9
         # ---- one roofline object per leading kernel; durations measured live (events attached to each dispatch) ----
         def k_ms(name):
             kk = tm["kernels"][name]
@@ -765,51 +837,25 @@ def main():
                     "longest_dispatch_on_any_stream": max(live, key=lambda k_: live[k_][0]),
                     "live_ms": {k_: {"ms": round(v_[0], 4), "stream": v_[1]} for k_, v_ in live.items()},
                     "measured": "HIP events attached to each dispatch in this run (reads-resident leg, 5 timed batches)"}
-        out = {
-            "metric": "150bp reads quasimapped/sec (whole node); bit-exact coverage",
-            "value": value, "unit": "reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong" if strong else "weak",
-            "vs_baseline": None, "dtype": "u32", "data": "synthetic",
-            "value_is": "SURVEY §8(d) region: host buffers in (2-bit planes, page-locked) -> H2D -> kernels -> (N > 1: one exchange) "
-                        "-> D2H: coverage arrays final on the host; distinct reads every step",
-            "timed_region": "changed in round 3: rounds 1-2 timed the kernel pipeline only (reads resident in HBM, one batch replayed, "
-                            "coverage left in HBM; that figure is the key `kernel_pipeline`), and N > 1 jobs do ONE exchange at the "
-                            "end of the job, not one per step: values of different rounds are not comparable",
-            "config": {"workload": "configs[1]: M. tuberculosis scale, 4411532 bp random ref + 60000 SNP PRG, k=10, "
-                                   f"{n} x 150 bp reads per GPU per step, fwd+rc, {NB} distinct batches cycled, reads handed over as "
-                                   + ("2-bit planes" if args.planes else "a 2-bit stream (37.5 B per read)") + " in page-locked host memory"
-                                   + ("" if args.upload_seeds else ", per-read seeds read in place from page-locked host memory")
-                                   + "; no skip plane (the synthetic reads hold no N: gmx.h takes a null skip pointer as 'none skipped')",
-                       "reads_per_gpu": n, "read_len": READ_LEN, "kmer_size": KMER, "distinct_batches": NB,
-                       "h2d_bytes_per_read": h2d_per_read,
-                       "parallelism": f"reads sharded x{world} by global read index, index replicated, one RCCL all-reduce of the "
-                                      "coverage block per JOB (after the last step), then D2H",
-                       "exchange": exchange, "index_build_s": round(t_index, 2), "reads_generation_s": round(t_reads, 2),
-                       "index_bytes": int(ix.info.index_bytes)},
-            "h2d_rate_GBps": h2d_gbs,
-            "jobs": {"n": len(job_seconds), "total_seconds": float(sum(job_seconds)), "value_is": "the median job (each job: exactly `steps` steps between fences; enough jobs for >= 1 s of timed work)",
-                     "min_value": total_reads / max(job_seconds), "max_value": total_reads / min(job_seconds),
-                     "p10_p90_values": [total_reads / float(np.percentile(job_seconds, 90)), total_reads / float(np.percentile(job_seconds, 10))],
-                     "first_values": [total_reads / x for x in job_seconds[:8]]},
-            "roofline": {
-                # what bounds the STEP: the host link. 37.5 B per read cross PCIe once; the kernels of a batch take less than
-                # half of the step (kernel_pipeline), the rest of the time the GPU waits for the next batch's bytes.
-                "bound": "pcie", "achieved": h2d_gbs, "peak": PCIE_PEAK_GBS, "unit": "GB/s", "frac": h2d_gbs / PCIE_PEAK_GBS,
-                "traffic": int(h2d_per_read * n),
-                "traffic_is": "bytes uploaded per step and GPU (exact: reads x h2d_bytes_per_read; no PMC counter sees the host link)",
-                "peak_source": "MI355X_MICROARCH.md: host link PCIe Gen5 x16, 63 GB/s (spec), per direction",
-                "step_ms": dt / args.steps * 1e3,
-                "kernels_ms_per_step": side.get("kernel_pipeline", {}).get("ms_per_step"),
-                "dominant_kernel": dominant["longest_on_the_main_chain"],
-                "dominant_kernel_is": dominant,
-                "kernels": kernel_rooflines,
-            },
-            "stats_job": st,
+        stats_job = out.pop("stats_job")   # (the keys in the order of the line before --full existed)
+        out["roofline"] = {
+            # what bounds the STEP: the host link. 37.5 B per read cross PCIe once; the kernels of a batch take less than
+            # half of the step (kernel_pipeline), the rest of the time the GPU waits for the next batch's bytes.
+            "bound": "pcie", "achieved": h2d_gbs, "peak": PCIE_PEAK_GBS, "unit": "GB/s", "frac": h2d_gbs / PCIE_PEAK_GBS,
+            "traffic": int(h2d_per_read * n),
+            "traffic_is": "bytes uploaded per step and GPU (exact: reads x h2d_bytes_per_read; no PMC counter sees the host link)",
+            "peak_source": "MI355X_MICROARCH.md: host link PCIe Gen5 x16, 63 GB/s (spec), per direction",
+            "step_ms": dt / args.steps * 1e3,
+            "kernels_ms_per_step": side.get("kernel_pipeline", {}).get("ms_per_step"),
+            "dominant_kernel": dominant["longest_on_the_main_chain"],
+            "dominant_kernel_is": dominant,
+            "kernels": kernel_rooflines,
         }
+        out["stats_job"] = stats_job
         out.update(side)
-        if per_rank is not None:
-            out["per_rank_s"] = per_rank
-            out["exchange_ms"] = exchange_ms
+    if rank == 0 and per_rank is not None:
+        out["per_rank_s"] = per_rank
+        out["exchange_ms"] = exchange_ms
     if extras:
         # ---- sustained: the same loop for >= 1 s --------------------------------------------------------------
         per_step = dt / args.steps
@@ -838,7 +884,7 @@ def main():
             except Exception as exc:  # a leg must not cost the headline
                 out["configs"][str(which)] = {"error": repr(exc)[:300]}
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(prg, reads, np.asarray(seeds))
         print(json.dumps(out))
     if world > 1:

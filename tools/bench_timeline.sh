@@ -3,7 +3,7 @@
 set -u
 export TMPDIR=/tmp
 OUT=${1:-gpurun_out/bt}; mkdir -p $OUT
-rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o trace -- python bench.py --no-extras --no-cpu-baseline --steps 10 --warmup 2 > $OUT/bench.txt 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o trace -- python bench.py --full --no-extras --no-cpu-baseline --steps 10 --warmup 2 > $OUT/bench.txt 2>&1
 python - <<PY
 import csv
 rows = sorted(csv.DictReader(open("$OUT/trace/trace_kernel_trace.csv")), key=lambda r: int(r["Start_Timestamp"]))
