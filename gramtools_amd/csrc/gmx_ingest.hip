@@ -25,6 +25,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -375,6 +376,105 @@ __device__ __attribute__((noinline)) uint64_t ing_rare(int kind, uint32_t e, uin
   return ((uint64_t)e1 << 32) | (bits - 1u);
 }
 
+// Kraft sum of the code lengths lens[0, n) in units of 2^-15: 2^15 for a complete code (the block finder's test)
+__device__ __attribute__((noinline)) uint32_t ing_kraft(const uint8_t *lens, uint32_t n) {
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t k = 0;
+  for (uint32_t s = lane; s < n; s += 64u) k += lens[s] ? (1u << 15) >> lens[s] : 0u;
+  for (int off = 32; off > 0; off >>= 1) k += __shfl_down(k, off);
+  return uni(k);
+}
+
+// The code tables of a fixed (btype 1) or dynamic (btype 2) block whose three header bits the reader has taken: 0, or
+// GMX_INGEST_BAD_MEMBER. `strict` (the gzip block finder): every code set complete as well.
+__device__ __forceinline__ uint32_t ing_block_tables(WaveLds &L, Bits &bs, uint32_t btype, bool strict) {
+  const uint32_t lane = threadIdx.x & 63u;
+  if (btype == 1) {  // fixed codes (§3.2.6)
+    for (uint32_t s0 = 0; s0 < 320u; s0 += 64u) {  // (lens[] has 320 entries; no lane-divergent branch inside the block loop, see the symbol loop)
+      const uint32_t s = s0 + lane;
+      L.lens[s] = s < 144u ? 8 : s < 256u ? 9 : s < 280u ? 7 : 8;
+    }
+    __syncthreads();
+    bool ok = uni(ing_build(L.lens, 288, L.lit, ING_LIT_ROOT, L.lit_sorted, L.lit_count, 0)) != 0;
+    L.lens[lane] = 5;  // (32 distance codes; the lanes above write lengths nobody reads)
+    __syncthreads();
+    ok = uni(ing_build(L.lens, 32, reinterpret_cast<uint32_t *>(L.dist), ING_DIST_ROOT, L.dist_sorted, L.dist_count, 1)) != 0 && ok;
+    if (!ok) {
+      return GMX_INGEST_BAD_MEMBER;
+    }
+  } else {  // dynamic codes (§3.2.7)
+    // (while the lengths are read a lane with nothing to write writes into lit_sorted[]: the block before is done with it, this one
+    // fills it when its lengths are complete; dummy[] shares its bytes with lens[])
+    uint8_t *const hdr_dummy = reinterpret_cast<uint8_t *>(L.lit_sorted) + lane;
+    const uint32_t hlit = bs.take(5) + 257u, hdist = bs.take(5) + 1u, hclen = bs.take(4) + 4u;
+    if (hlit > 286u || hdist > 30u) {
+      return GMX_INGEST_BAD_MEMBER;
+    }
+    *(lane < 19u ? &L.lens[lane] : hdr_dummy) = 0;
+    __syncthreads();
+    for (uint32_t i = 0; i < hclen; ++i) {
+      bs.refill();
+      const uint32_t v = bs.take(3);
+      // order of the code-length code's lengths: 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15
+      const uint32_t sym = i < 3u ? 16u + i : i == 3u ? 0u : (i & 1u) ? 8u - ((i - 3u) >> 1) : 8u + ((i - 4u) >> 1) + 0u;
+      *(lane == 0 ? &L.lens[sym] : hdr_dummy) = (uint8_t)v;
+    }
+    __syncthreads();
+    // (the code-length code's table borrows the distance table: root 7, every code at most 7 bits)
+    uint32_t *const cl_tab = reinterpret_cast<uint32_t *>(L.dist);
+    if (!uni(ing_build(L.lens, 19, cl_tab, 7, L.dist_sorted, L.dist_count, 2))) {
+      return GMX_INGEST_BAD_MEMBER;
+    }
+    if (strict && uni(ing_kraft(L.lens, 19)) != (1u << 15)) return GMX_INGEST_BAD_MEMBER;
+    const uint32_t total = hlit + hdist;
+    uint32_t at = 0, prev = 0;
+    while (at < total) {
+      bs.refill();
+      const uint32_t e = uni(cl_tab[bs.peek(7)]);
+      if ((e & 15u) == 0) {
+        return GMX_INGEST_BAD_MEMBER;
+      }
+      bs.drop(e & 15u);
+      const uint32_t sym = e >> 8;
+      uint32_t rep = 1, val = sym;
+      if (sym == 16u) {
+        if (at == 0) {
+          return GMX_INGEST_BAD_MEMBER;
+        }
+        rep = 3u + bs.take(2);
+        val = prev;
+      } else if (sym == 17u) {
+        rep = 3u + bs.take(3);
+        val = 0;
+      } else if (sym == 18u) {
+        rep = 11u + bs.take(7);
+        val = 0;
+      }
+      if (at + rep > total) {
+        return GMX_INGEST_BAD_MEMBER;
+      }
+      for (uint32_t i0 = 0; i0 < rep; i0 += 64u) *(i0 + lane < rep ? &L.lens[at + i0 + lane] : hdr_dummy) = (uint8_t)val;  // (lens[0, 19) held the code-length code's lengths: its table is built)
+      at += rep;
+      prev = val;
+    }
+    for (uint32_t i0 = total; i0 < 320u; i0 += 64u) *(i0 + lane < 320u ? &L.lens[i0 + lane] : hdr_dummy) = 0;
+    __syncthreads();
+    if (uni(L.lens[256]) == 0) {  // no end-of-block code
+      return GMX_INGEST_BAD_MEMBER;
+    }
+    if (strict) {  // complete literal/length code; a complete distance code, or a single distance code (RFC 1951 §3.2.7)
+      const uint32_t kd = uni(ing_kraft(L.lens + hlit, hdist));
+      if (uni(ing_kraft(L.lens, hlit)) != (1u << 15) || (kd != (1u << 15) && kd != (1u << 14))) return GMX_INGEST_BAD_MEMBER;
+    }
+    bool ok = uni(ing_build(L.lens, hlit, L.lit, ING_LIT_ROOT, L.lit_sorted, L.lit_count, 0)) != 0;
+    ok = uni(ing_build(L.lens + hlit, hdist, reinterpret_cast<uint32_t *>(L.dist), ING_DIST_ROOT, L.dist_sorted, L.dist_count, 1)) != 0 && ok;
+    if (!ok) {
+      return GMX_INGEST_BAD_MEMBER;
+    }
+  }
+  return 0;
+}
+
 // CRC-32 (IEEE, reflected) as polynomial arithmetic: a * b mod P, and x^n mod P (zlib's crc32_combine does the same)
 #define ING_CRC_POLY 0xedb88320u
 __device__ __forceinline__ uint32_t ing_mulmod(uint32_t a, uint32_t b) {
@@ -408,6 +508,67 @@ typedef uint32_t ing_v4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) ing_v4 ing_g128;
 __device__ __forceinline__ uint8_t ing_load_coherent(const ing_g8 *p) {  // text this wave stored earlier: past the vector L1
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The four slicing-by-4 tables of CRC-32 (4 KB) into crc_tab (LDS), by the wave
+__device__ __forceinline__ void ing_crc_tables(uint32_t *crc_tab) {
+  const uint32_t lane = threadIdx.x & 63u;
+  for (uint32_t i = lane; i < 256u; i += 64u) {
+    uint32_t c = i;
+    for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ ING_CRC_POLY : c >> 1;
+    crc_tab[i] = c;
+  }
+  __syncthreads();
+  for (uint32_t t = 1; t < 4u; ++t) {
+    for (uint32_t i = lane; i < 256u; i += 64u) {
+      const uint32_t v = crc_tab[(t - 1u) * 256u + i];
+      crc_tab[t * 256u + i] = (v >> 8) ^ crc_tab[v & 0xFFu];
+    }
+    __syncthreads();
+  }
+}
+// CRC register of bytes [first, total) of al (al 16-byte aligned): 64 slices side by side, four table look-ups per word, then the
+// slices' registers combined pairwise; the register starts from `init` (0xFFFFFFFF: a member's CRC-32 is ~ the result; 0: the
+// part's share, linear in its bytes, for ing_mulmod / ing_xpow8 to combine). Wave-uniform result.
+__device__ __forceinline__ uint32_t ing_crc_wave(const uint32_t *crc_tab, const ing_g8 *al, uint32_t first, uint32_t total, uint32_t init) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t per = (((total + 63u) / 64u) + 3u) & ~3u;
+  // (EVERY lane's slice starts at the member's first byte at the earliest — `first` bytes above the boundary: with only lane 0
+  //  clamped, a member of a few hundred bytes that does not start on a 16-byte boundary had the bytes in front of it hashed
+  //  by lanes 1.. and was reported as GMX_INGEST_BAD_CRC)
+  uint32_t lo = min(total, max(first, lane * per));
+  const uint32_t hi = max(lo, min(total, (lane + 1u) * per));
+  uint32_t c = lane == 0 ? init : 0u;
+  const uint32_t n = hi > lo ? hi - lo : 0u;
+  auto byte_step = [&](uint32_t at) { c = crc_tab[(c ^ ing_load_coherent(al + at)) & 0xFFu] ^ (c >> 8); };
+  while (lo < hi && (lo & 3u)) byte_step(lo++);
+  const ing_g32 *words = (const ing_g32 *)al;
+  for (; lo + 16u <= hi; lo += 16u) {  // four words in flight
+    const uint32_t w0 = __hip_atomic_load(words + lo / 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
+                   w1 = __hip_atomic_load(words + lo / 4u + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
+                   w2 = __hip_atomic_load(words + lo / 4u + 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
+                   w3 = __hip_atomic_load(words + lo / 4u + 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t ws[4] = {w0, w1, w2, w3};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      c ^= ws[q];
+      c = crc_tab[768u + (c & 0xFFu)] ^ crc_tab[512u + ((c >> 8) & 0xFFu)] ^ crc_tab[256u + ((c >> 16) & 0xFFu)] ^ crc_tab[c >> 24];
+    }
+  }
+  for (; lo + 4u <= hi; lo += 4u) {
+    c ^= __hip_atomic_load(words + lo / 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    c = crc_tab[768u + (c & 0xFFu)] ^ crc_tab[512u + ((c >> 8) & 0xFFu)] ^ crc_tab[256u + ((c >> 16) & 0xFFu)] ^ crc_tab[c >> 24];
+  }
+  while (lo < hi) byte_step(lo++);
+  uint32_t nn = n;
+  for (uint32_t dlt = 1; dlt < 64u; dlt <<= 1) {  // register of (left part || right part) = left * x^(8 |right|) + right
+    const uint32_t c_r = __shfl_down(c, dlt), n_r = __shfl_down(nn, dlt);
+    if ((lane & (2u * dlt - 1u)) == 0) {
+      c = (n_r ? ing_mulmod(c, ing_xpow8(n_r)) : c) ^ c_r;
+      nn += n_r;
+    }
+  }
+  return uni(c);
 }
 
 // [lo, hi) within one KB of the window -> memory; the member's first and last pieces: a neighbour owns the rest of a 16-byte piece
@@ -536,93 +697,8 @@ __device__ __forceinline__ void ing_inflate_member(WaveLds &L, const uint32_t *_
       err = GMX_INGEST_BAD_MEMBER;
       break;
     }
-    if (btype == 1) {  // fixed codes (§3.2.6)
-      for (uint32_t s0 = 0; s0 < 320u; s0 += 64u) {  // (lens[] has 320 entries; no lane-divergent branch inside the block loop, see the symbol loop)
-        const uint32_t s = s0 + lane;
-        L.lens[s] = s < 144u ? 8 : s < 256u ? 9 : s < 280u ? 7 : 8;
-      }
-      __syncthreads();
-      bool ok = uni(ing_build(L.lens, 288, L.lit, ING_LIT_ROOT, L.lit_sorted, L.lit_count, 0)) != 0;
-      L.lens[lane] = 5;  // (32 distance codes; the lanes above write lengths nobody reads)
-      __syncthreads();
-      ok = uni(ing_build(L.lens, 32, reinterpret_cast<uint32_t *>(L.dist), ING_DIST_ROOT, L.dist_sorted, L.dist_count, 1)) != 0 && ok;
-      if (!ok) {
-        err = GMX_INGEST_BAD_MEMBER;
-        break;
-      }
-    } else {  // dynamic codes (§3.2.7)
-      // (while the lengths are read a lane with nothing to write writes into lit_sorted[]: the block before is done with it, this one
-      // fills it when its lengths are complete; dummy[] shares its bytes with lens[])
-      uint8_t *const hdr_dummy = reinterpret_cast<uint8_t *>(L.lit_sorted) + lane;
-      const uint32_t hlit = bs.take(5) + 257u, hdist = bs.take(5) + 1u, hclen = bs.take(4) + 4u;
-      if (hlit > 286u || hdist > 30u) {
-        err = GMX_INGEST_BAD_MEMBER;
-        break;
-      }
-      *(lane < 19u ? &L.lens[lane] : hdr_dummy) = 0;
-      __syncthreads();
-      for (uint32_t i = 0; i < hclen; ++i) {
-        bs.refill();
-        const uint32_t v = bs.take(3);
-        // order of the code-length code's lengths: 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15
-        const uint32_t sym = i < 3u ? 16u + i : i == 3u ? 0u : (i & 1u) ? 8u - ((i - 3u) >> 1) : 8u + ((i - 4u) >> 1) + 0u;
-        *(lane == 0 ? &L.lens[sym] : hdr_dummy) = (uint8_t)v;
-      }
-      __syncthreads();
-      // (the code-length code's table borrows the distance table: root 7, every code at most 7 bits)
-      uint32_t *const cl_tab = reinterpret_cast<uint32_t *>(L.dist);
-      if (!uni(ing_build(L.lens, 19, cl_tab, 7, L.dist_sorted, L.dist_count, 2))) {
-        err = GMX_INGEST_BAD_MEMBER;
-        break;
-      }
-      const uint32_t total = hlit + hdist;
-      uint32_t at = 0, prev = 0;
-      while (at < total && !err) {
-        bs.refill();
-        const uint32_t e = uni(cl_tab[bs.peek(7)]);
-        if ((e & 15u) == 0) {
-          err = GMX_INGEST_BAD_MEMBER;
-          break;
-        }
-        bs.drop(e & 15u);
-        const uint32_t sym = e >> 8;
-        uint32_t rep = 1, val = sym;
-        if (sym == 16u) {
-          if (at == 0) {
-            err = GMX_INGEST_BAD_MEMBER;
-            break;
-          }
-          rep = 3u + bs.take(2);
-          val = prev;
-        } else if (sym == 17u) {
-          rep = 3u + bs.take(3);
-          val = 0;
-        } else if (sym == 18u) {
-          rep = 11u + bs.take(7);
-          val = 0;
-        }
-        if (at + rep > total) {
-          err = GMX_INGEST_BAD_MEMBER;
-          break;
-        }
-        for (uint32_t i0 = 0; i0 < rep; i0 += 64u) *(i0 + lane < rep ? &L.lens[at + i0 + lane] : hdr_dummy) = (uint8_t)val;  // (lens[0, 19) held the code-length code's lengths: its table is built)
-        at += rep;
-        prev = val;
-      }
-      if (err) break;
-      for (uint32_t i0 = total; i0 < 320u; i0 += 64u) *(i0 + lane < 320u ? &L.lens[i0 + lane] : hdr_dummy) = 0;
-      __syncthreads();
-      if (uni(L.lens[256]) == 0) {  // no end-of-block code
-        err = GMX_INGEST_BAD_MEMBER;
-        break;
-      }
-      bool ok = uni(ing_build(L.lens, hlit, L.lit, ING_LIT_ROOT, L.lit_sorted, L.lit_count, 0)) != 0;
-      ok = uni(ing_build(L.lens + hlit, hdist, reinterpret_cast<uint32_t *>(L.dist), ING_DIST_ROOT, L.dist_sorted, L.dist_count, 1)) != 0 && ok;
-      if (!ok) {
-        err = GMX_INGEST_BAD_MEMBER;
-        break;
-      }
-    }
+    err = ing_block_tables(L, bs, btype, false);
+    if (err) break;
     ing_fuse(L.lit, ING_LIT_ROOT);
     if (STATS) t_build += clock64() - t_b0;
     // ---- the block's symbols ----
@@ -712,57 +788,9 @@ __device__ __forceinline__ void ing_inflate_member(WaveLds &L, const uint32_t *_
     uint32_t *const crc_tab = reinterpret_cast<uint32_t *>(&L);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
-    for (uint32_t i = lane; i < 256u; i += 64u) {
-      uint32_t c = i;
-      for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ ING_CRC_POLY : c >> 1;
-      crc_tab[i] = c;
-    }
-    __syncthreads();
-    for (uint32_t t = 1; t < 4u; ++t) {
-      for (uint32_t i = lane; i < 256u; i += 64u) {
-        const uint32_t v = crc_tab[(t - 1u) * 256u + i];
-        crc_tab[t * 256u + i] = (v >> 8) ^ crc_tab[v & 0xFFu];
-      }
-      __syncthreads();
-    }
+    ing_crc_tables(crc_tab);
     // slices of whole words, counted like everything else from the 16-byte boundary below the member's first byte
-    const uint32_t total = end_v;
-    const uint32_t per = (((total + 63u) / 64u) + 3u) & ~3u;
-    // (EVERY lane's slice starts at the member's first byte at the earliest — `mis` bytes above the boundary: with only lane 0
-    //  clamped, a member of a few hundred bytes that does not start on a 16-byte boundary had the bytes in front of it hashed
-    //  by lanes 1.. and was reported as GMX_INGEST_BAD_CRC)
-    uint32_t lo = min(total, max(mis, lane * per));
-    const uint32_t hi = max(lo, min(total, (lane + 1u) * per));
-    uint32_t c = lane == 0 ? 0xFFFFFFFFu : 0u;
-    const uint32_t n = hi > lo ? hi - lo : 0u;
-    auto byte_step = [&](uint32_t at) { c = crc_tab[(c ^ ing_load_coherent(al + at)) & 0xFFu] ^ (c >> 8); };
-    while (lo < hi && (lo & 3u)) byte_step(lo++);
-    const ing_g32 *words = (const ing_g32 *)al;
-    for (; lo + 16u <= hi; lo += 16u) {  // four words in flight
-      const uint32_t w0 = __hip_atomic_load(words + lo / 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
-                     w1 = __hip_atomic_load(words + lo / 4u + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
-                     w2 = __hip_atomic_load(words + lo / 4u + 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
-                     w3 = __hip_atomic_load(words + lo / 4u + 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const uint32_t ws[4] = {w0, w1, w2, w3};
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        c ^= ws[q];
-        c = crc_tab[768u + (c & 0xFFu)] ^ crc_tab[512u + ((c >> 8) & 0xFFu)] ^ crc_tab[256u + ((c >> 16) & 0xFFu)] ^ crc_tab[c >> 24];
-      }
-    }
-    for (; lo + 4u <= hi; lo += 4u) {
-      c ^= __hip_atomic_load(words + lo / 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      c = crc_tab[768u + (c & 0xFFu)] ^ crc_tab[512u + ((c >> 8) & 0xFFu)] ^ crc_tab[256u + ((c >> 16) & 0xFFu)] ^ crc_tab[c >> 24];
-    }
-    while (lo < hi) byte_step(lo++);
-    uint32_t nn = n;
-    for (uint32_t dlt = 1; dlt < 64u; dlt <<= 1) {  // register of (left part || right part) = left * x^(8 |right|) + right
-      const uint32_t c_r = __shfl_down(c, dlt), n_r = __shfl_down(nn, dlt);
-      if ((lane & (2u * dlt - 1u)) == 0) {
-        c = (n_r ? ing_mulmod(c, ing_xpow8(n_r)) : c) ^ c_r;
-        nn += n_r;
-      }
-    }
+    const uint32_t c = ing_crc_wave(crc_tab, al, mis, end_v, 0xFFFFFFFFu);
     if (uni(~c) != uni(members[mi].crc)) err = GMX_INGEST_BAD_CRC;
   }
   if (STATS && dbg && lane == 0) {
@@ -793,8 +821,8 @@ gmx_inflate_kernel(const uint32_t *__restrict__ comp, const IngestMember *__rest
 // the chunk's text -> records -> bit planes
 // ------------------------------------------------------------------------------------------------------------------
 // starts a chunk: the incomplete last record of the chunk before (prev; null: a file's first chunk) in front of this one's text
-__global__ void gmx_carry_kernel(const IngestState *prev, const uint8_t *prev_text, IngestState *cur, uint8_t *cur_text, uint32_t members_text,
-                                 uint32_t final_chunk, uint32_t host_tail) {
+__device__ __forceinline__ void ing_carry(const IngestState *prev, const uint8_t *prev_text, IngestState *cur, uint8_t *cur_text, uint32_t members_text,
+                                          uint32_t final_chunk, uint32_t host_tail) {
   uint32_t tail = host_tail;  // (gmx_ingest_scan: the caller has put that many bytes in front of the chunk's text already)
   if (prev) {
     tail = prev->tail_len;
@@ -820,6 +848,16 @@ __global__ void gmx_carry_kernel(const IngestState *prev, const uint8_t *prev_te
     for (int i = 0; i < 16; ++i) cur->sub_pairs[i] = 0;
     cur->final_chunk = final_chunk;
   }
+}
+
+__global__ void gmx_carry_kernel(const IngestState *prev, const uint8_t *prev_text, IngestState *cur, uint8_t *cur_text, uint32_t members_text,
+                                 uint32_t final_chunk, uint32_t host_tail) {
+  ing_carry(prev, prev_text, cur, cur_text, members_text, final_chunk, host_tail);
+}
+// the same for a plain gzip chunk: its text length is on the device (gmx_gz_link_kernel / gmx_gz_check_kernel)
+__global__ void gmx_carry_gz_kernel(const IngestState *prev, const uint8_t *prev_text, IngestState *cur, uint8_t *cur_text, const uint32_t *members_text,
+                                    uint32_t final_chunk) {
+  ing_carry(prev, prev_text, cur, cur_text, *members_text, final_chunk, 0u);
 }
 
 #define ING_TILE 4096u  // bytes of text per 256-thread block of the newline kernels (16 per thread)
@@ -1080,6 +1118,588 @@ __global__ void __launch_bounds__(256) gmx_fq_pack_kernel(const uint8_t *text, I
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// plain gzip (one deflate stream per member, members concatenated): the chunk's compressed bytes cut into PIECES decoded side
+// by side, with the rules of gmx_pargz.h:
+//   gmx_gz_decode_kernel   one wavefront per piece. The first piece of a file starts behind the gzip header, the first of a later
+//                          chunk where the chunk before ended (on the device); any other piece searches a block start from its
+//                          nominal bit: 64 bit positions at a time through the 17-bit screen, then a trial decode of the whole
+//                          block (complete codes, text only, >= 1 KB, a plausible header behind it). Output: 16-bit symbols, a
+//                          byte or "byte j of the 32 KB in front of the piece" (256 + j); back-references copy them along. The
+//                          piece stops at the first block end at or beyond the next piece's nominal start; member ends (trailer,
+//                          next header) are recorded on the way.
+//   gmx_gz_link_kernel     one wavefront walks the pieces in order: a piece counts when it starts exactly where the one before
+//                          ended; one that does not is decoded again from that end (the repair: all on the device). Text offsets.
+//   gmx_gz_window_kernel   one block: the last 32 KB in front of every piece, in order (LDS, double-buffered)
+//   gmx_gz_resolve_kernel  symbols -> bytes at the piece's text offset, where the record scan expects them
+//   gmx_gz_crc_kernel      one wavefront per piece: CRC-32 of its text between member ends (and x^(8 n) to combine them)
+//   gmx_gz_check_kernel    the parts combined in order and checked against every member's trailer (CRC-32 and ISIZE)
+// ------------------------------------------------------------------------------------------------------------------
+#define GZ_WIN 32768u    // deflate's window
+#define GZ_ENDS 16u      // member ends one piece can record
+#define GZ_RING 1024u    // 16-bit symbols in the LDS window (the 2 KB of WaveLds::ring)
+#define GZ_RING_MASK (GZ_RING - 1u)
+#define GZ_FLUSH 256u    // symbols per store of the window to memory (8 bytes per lane)
+#define GZ_NEAR_MAX (GZ_RING - 320u)  // distances up to this are served from the LDS window
+// what a piece's decode met (GzPiece::flags)
+#define GZP_FOUND 1u     // decoding started (a searched start passed the block test)
+#define GZP_EOS 2u       // the stream's end: the last member's trailer, then nothing or zeros
+#define GZP_CAPPED 4u    // the piece's output passed its bound
+#define GZP_OVERRUN 8u   // bytes needed beyond the chunk's (look-ahead included)
+#define GZP_ENDS 16u     // more member ends than GZ_ENDS
+#define GZP_BAD 32u      // not deflate / gzip here
+
+struct GzPiece {
+  uint32_t start, end;  // bits within the chunk's bytes: where decoding started, where it stopped
+  uint32_t n_sym, flags, n_ends, text_off;
+  uint32_t end_at[GZ_ENDS], end_crc[GZ_ENDS], end_isize[GZ_ENDS];  // member ends: symbol index, the trailer's CRC-32 and ISIZE
+  uint32_t seg_crc[GZ_ENDS + 1], seg_pow[GZ_ENDS + 1];             // the text between them: CRC register from 0, x^(8 length)
+};
+struct GzState {  // one per ingest: where the stream stands between chunks
+  uint32_t bit;              // in the next chunk's bytes
+  uint32_t eos;              // the stream has ended: what follows (from `bit` on) must be zeros
+  uint32_t run_crc, run_len;  // the open member's CRC register and length so far
+  uint32_t text_len;         // text of the chunk (the carry kernel's members_text)
+  uint32_t flags;            // GMX_INGEST_* of the chunk
+  uint32_t n_pieces;         // pieces in the chunk's chain
+  uint32_t repairs;          // pieces decoded again from their predecessor's end, since the ingest was created
+};
+struct GzArgs {
+  const uint32_t *comp;
+  uint32_t n_bytes, n_own, final_chunk, fresh;
+  uint32_t piece_bits, n_pieces, cap;  // nominal piece length; pieces; symbols a piece may write
+  uint16_t *sym;
+  GzPiece *pieces;
+  GzState *st;
+  uint32_t debug;               // GMX_GZ_DEBUG=1: the link kernel prints every piece
+  uint32_t late_mod, drop_mod;  // test hook (GMX_GZ_TEST_FIND): pieces i % late_mod == 0 take the block start behind the true one,
+                                // pieces i % drop_mod == drop_mod - 1 find none
+};
+typedef __attribute__((address_space(1))) uint16_t ing_g16;
+typedef uint32_t ing_v2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(1))) ing_v2 ing_g64;
+
+__device__ __forceinline__ uint32_t gz_byte(const GzArgs &a, uint32_t at) { return at < a.n_bytes ? (uint32_t)reinterpret_cast<const uint8_t *>(a.comp)[at] : 0u; }
+__device__ __forceinline__ uint32_t gz_le32(const GzArgs &a, uint32_t at) {
+  return gz_byte(a, at) | gz_byte(a, at + 1u) << 8 | gz_byte(a, at + 2u) << 16 | gz_byte(a, at + 3u) << 24;
+}
+__device__ __forceinline__ uint32_t gz_stop_bit(const GzArgs &a, uint32_t i) {
+  if (i + 1u < a.n_pieces) return (i + 1u) * a.piece_bits;
+  return a.final_chunk ? 0xFFFFFFFFu : a.n_own * 8u;
+}
+// a gzip member header at byte `at` of b[0, n) (RFC 1952 §2.3): the byte behind it, or 0 with *why = GZP_BAD / GZP_OVERRUN
+// (arguments by value: a reference to the kernel's GzArgs would put a copy of them in private memory, read per lane)
+__device__ __attribute__((noinline)) uint32_t gz_header(const uint8_t *b, uint32_t n, uint32_t fin, uint32_t at, uint32_t *why) {
+  auto byte = [&](uint32_t i) { return i < n ? (uint32_t)b[i] : 0u; };
+  if (at + 10u > n) {
+    *why = fin ? GZP_BAD : GZP_OVERRUN;
+    return 0;
+  }
+  const uint32_t flg = byte(at + 3u);
+  if (byte(at) != 0x1fu || byte(at + 1u) != 0x8bu || byte(at + 2u) != 8u || (flg & 0xE0u)) {
+    *why = GZP_BAD;
+    return 0;
+  }
+  uint32_t p = at + 10u;
+  if (flg & 4u) p += 2u + (byte(p) | byte(p + 1u) << 8);  // FEXTRA
+  if (flg & 8u) {                                        // FNAME
+    while (p < n && byte(p)) ++p;
+    ++p;
+  }
+  if (flg & 16u) {  // FCOMMENT
+    while (p < n && byte(p)) ++p;
+    ++p;
+  }
+  if (flg & 2u) p += 2u;  // FHCRC
+  if (p > n) {
+    *why = fin ? GZP_BAD : GZP_OVERRUN;
+    return 0;
+  }
+  return p;
+}
+// bytes [at, n) of b all zero (the padding some writers leave behind the last member)
+__device__ __attribute__((noinline)) bool gz_zeros(const uint8_t *b, uint32_t n, uint32_t at) {
+  bool nz = false;
+  for (uint32_t i = at + (threadIdx.x & 63u); i < n; i += 64u) nz = nz || b[i] != 0;
+  return __ballot(nz) == 0;
+}
+__device__ __forceinline__ uint16_t gz_load_coherent(const ing_g16 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+struct GzDone {  // what gz_decode leaves (also in a.pieces[pi]; the link kernel goes on with these, not with its own stores)
+  uint32_t flags, end, n_sym;
+};
+// Piece `pi` from bit `start` until a block ends at or beyond `stop` (or the stream ends). header_first: a member header stands at
+// `start` (the file's first). trial: the first block must pass the block finder's tests (else the result is 0 and nothing is
+// recorded). Results (lane 0's vector stores) into a.pieces[pi].
+__device__ __forceinline__ GzDone gz_decode(WaveLds &L, const GzArgs &a, uint32_t pi, uint32_t start, bool header_first, bool trial, bool late) {
+  const uint32_t lane = threadIdx.x & 63u;
+  // (the values the scalar decoder works with are made wave-uniform first, as everything else in it)
+  pi = uni(pi);
+  start = uni(start);
+  header_first = uni(header_first ? 1u : 0u) != 0;
+  trial = uni(trial ? 1u : 0u) != 0;
+  late = uni(late ? 1u : 0u) != 0;
+  uint16_t *const ring = reinterpret_cast<uint16_t *>(L.ring);
+  uint16_t *const dummy = reinterpret_cast<uint16_t *>(L.lens);  // (lens[] is dead in the symbol loop and the copies)
+  ing_g16 *const out = (ing_g16 *)(a.sym + (size_t)pi * a.cap);
+  GzPiece *const pc = a.pieces + pi;
+  const uint32_t cap = uni(a.cap), stop = uni(gz_stop_bit(a, pi)), nb = uni(a.n_bytes), fin = uni(a.final_chunk);
+  uint32_t out_pos = 0, flushed = 0, n_ends = 0, flags = GZP_FOUND, pos = start;
+  int mstart = -(int)GZ_WIN;  // references may not reach below this (a member's first symbol: an empty window)
+  auto ring_reset = [&]() {  // the slots of positions [-1024, 0): placeholders for the window in front of the piece
+    for (uint32_t k = lane; k < GZ_RING; k += 64u) ring[k] = (uint16_t)(256u + GZ_WIN - GZ_RING + k);
+  };
+  ring_reset();
+  auto flush_to = [&](uint32_t upto) {  // [flushed, upto), upto a multiple of GZ_FLUSH
+    for (uint32_t blk = flushed; blk < upto; blk += GZ_FLUSH)
+      *(ing_g64 *)(out + blk + 4u * lane) = *reinterpret_cast<const ing_v2 *>(&ring[(blk + 4u * lane) & GZ_RING_MASK]);
+    flushed = upto;
+  };
+  auto flush_rest = [&]() {  // [flushed, out_pos) symbol by symbol (`flushed` stays: the next flush_to stores them again, unchanged)
+    for (uint32_t k = flushed + lane; k < out_pos; k += 64u) out[k] = ring[k & GZ_RING_MASK];
+  };
+  auto copy_match = [&](uint32_t len, uint32_t dist) {
+    uint32_t i0 = 0;
+    if (dist > GZ_NEAR_MAX) {  // from the symbols already stored (every position read lies below `flushed`), or the window's placeholders
+      do {
+        const uint32_t i = i0 + lane;
+        const int src = (int)(out_pos - dist + i);
+        const uint16_t v = src < 0 ? (uint16_t)(256 + (int)GZ_WIN + src) : gz_load_coherent(out + min((uint32_t)src, out_pos));
+        *(i < len ? &ring[(out_pos + i) & GZ_RING_MASK] : &dummy[lane]) = v;
+        i0 += 64u;
+      } while (i0 < len);
+    } else if (dist >= len) {
+      do {
+        const uint32_t i = i0 + lane;
+        const uint16_t v = ring[(out_pos - dist + i) & GZ_RING_MASK];
+        *(i < len ? &ring[(out_pos + i) & GZ_RING_MASK] : &dummy[lane]) = v;
+        i0 += 64u;
+      } while (i0 < len);
+    } else {
+      do {
+        const uint32_t i = i0 + lane;
+        const uint16_t v = ring[(out_pos - dist + i % dist) & GZ_RING_MASK];
+        *(i < len ? &ring[(out_pos + i) & GZ_RING_MASK] : &dummy[lane]) = v;
+        i0 += 64u;
+      } while (i0 < len);
+    }
+    out_pos += len;
+    if ((out_pos & ~(GZ_FLUSH - 1u)) > flushed) flush_to(out_pos & ~(GZ_FLUSH - 1u));
+  };
+  Bits bs;
+  bs.limit = (nb + 3u) / 4u;  // (the words behind the chunk's bytes read as zero)
+  if (header_first) {
+    uint32_t why = 0;
+    const uint32_t p = uni(gz_header(reinterpret_cast<const uint8_t *>(a.comp), nb, fin, start >> 3, &why));
+    if (!p) {
+      flags |= uni(why);
+      goto done;
+    }
+    pos = p * 8u;
+    mstart = 0;
+  }
+  bs.start(a.comp, pos >> 3);
+  bs.drop(pos & 7u);
+  for (bool first = true;; first = false) {
+    bs.refill();
+    const uint32_t last = bs.take(1), btype = bs.take(2);
+    uint32_t bad = 0;
+    if (btype == 0) {  // stored
+      bs.drop(bs.cnt & 7u);
+      bs.refill();
+      const uint32_t len = bs.take(16), nlen = bs.take(16);
+      const uint32_t from = bs.byte_pos();
+      if ((len ^ nlen) != 0xFFFFu) {
+        bad = GZP_BAD;
+      } else if (from + len > nb) {
+        bad = fin ? GZP_BAD : GZP_OVERRUN;
+      } else if (out_pos + len > cap) {
+        bad = GZP_CAPPED;
+      } else {
+        const uint8_t *src = reinterpret_cast<const uint8_t *>(a.comp) + from;
+        for (uint32_t i0 = 0; i0 < len; i0 += 64u) {
+          const uint32_t n = min(64u, len - i0);
+          *(lane < n ? &ring[(out_pos + lane) & GZ_RING_MASK] : &dummy[lane]) = src[i0 + min(lane, n - 1u)];
+          out_pos += n;
+          if ((out_pos & ~(GZ_FLUSH - 1u)) > flushed) flush_to(out_pos & ~(GZ_FLUSH - 1u));
+        }
+        bs.start(a.comp, from + len);
+      }
+    } else if (btype == 3u) {
+      bad = GZP_BAD;
+    } else if (ing_block_tables(L, bs, btype, trial && first)) {
+      bad = GZP_BAD;
+    } else {
+      ing_fuse(L.lit, ING_LIT_ROOT);
+      uint32_t stop_c = 0;  // 1 damaged, 2 the block's end, 3 the piece's bound
+      do {
+        bs.refill();
+        uint32_t e = uni(L.lit[ing_vpeek<ING_LIT_ROOT>((uint32_t)bs.buf)]);
+        if (__builtin_expect((int32_t)e < 0, 0)) {
+          const uint64_t rr = ing_rare(0, e, bs.buf, L.lit_count, L.lit_sorted);
+          const uint32_t r_lo = uni((uint32_t)rr);
+          bs.drop(r_lo & 0xFFu);
+          stop_c = r_lo >> 8;
+          e = uni((uint32_t)(rr >> 32));
+        }
+        if ((e & ING_LENGTH) == 0) {
+          const uint32_t n_lit = (e >> 6) & 3u;
+          bs.drop(e & 15u);
+          if (__builtin_expect(out_pos + n_lit > cap, 0)) {
+            stop_c = 3u;
+          } else {
+            *(lane < n_lit ? &ring[(out_pos + lane) & GZ_RING_MASK] : &dummy[lane]) = (uint16_t)((e >> (8u + 8u * (lane & 3u))) & 0xFFu);
+            out_pos += n_lit;
+            if (__builtin_expect((out_pos & ~(GZ_FLUSH - 1u)) > flushed, 0)) flush_to(out_pos & ~(GZ_FLUSH - 1u));
+          }
+        } else {
+          const uint32_t len = ((e >> 6) & 0x1FFu) + ing_sbfe((uint32_t)bs.buf, e);
+          bs.drop(e >> 23);
+          bs.refill();
+          const uint64_t de = L.dist[ing_vpeek<ING_DIST_ROOT>((uint32_t)bs.buf)];
+          const uint32_t d = uni((uint32_t)de);
+          uint32_t dist;
+          if (__builtin_expect((int32_t)d < 0, 0)) {
+            const uint64_t rr = ing_rare(1, d, bs.buf, L.dist_count, L.dist_sorted);
+            const uint32_t r_lo = uni((uint32_t)rr);
+            bs.drop(r_lo & 0xFFu);
+            stop_c = r_lo >> 8;
+            dist = uni((uint32_t)(rr >> 32));
+          } else {
+            dist = uni((uint32_t)(de >> 32)) + ing_sbfe((uint32_t)bs.buf, d);
+            bs.drop(d >> 23);
+          }
+          if (__builtin_expect((int)(out_pos - dist) < mstart, 0)) {
+            stop_c = 1u;
+          } else if (__builtin_expect(out_pos + len > cap, 0)) {
+            stop_c = 3u;
+          } else {
+            copy_match(len, dist);
+          }
+        }
+        asm volatile("" : "+s"(stop_c));
+      } while (stop_c == 0);
+      bad = stop_c == 1u ? GZP_BAD : stop_c == 3u ? GZP_CAPPED : 0u;
+    }
+    pos = bs.next_word() * 32u - bs.cnt;
+    if (pos > nb * 8u) bad = fin ? GZP_BAD : GZP_OVERRUN;  // (zeros decoded from behind the bytes: whatever else went wrong came of that)
+    if (trial && first) {  // the block finder's tests: a whole non-final block of >= 1 KB of text, a plausible header behind it
+      bool ok = !bad && !last && out_pos >= 1024u;
+      if (ok) {
+        flush_rest();
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        bool nt = false;
+        for (uint32_t k = lane; k < out_pos; k += 64u) {
+          const uint32_t c = gz_load_coherent(out + k);
+          nt = nt || (c < 256u && !((c >= 0x20u && c < 0x7Fu) || c == '\n' || c == '\r' || c == '\t'));
+        }
+        ok = __ballot(nt) == 0;
+      }
+      if (ok) {
+        Bits nx = bs;
+        nx.refill();
+        const uint32_t h = nx.take(3), type = h >> 1;
+        if (type == 3u) {
+          ok = false;
+        } else if (type == 2u) {
+          ok = nx.take(5) <= 29u && nx.take(5) <= 29u;
+        } else if (type == 0u) {
+          nx.drop(nx.cnt & 7u);
+          nx.refill();
+          const uint32_t len = nx.take(16), nlen = nx.take(16);
+          ok = (len ^ nlen) == 0xFFFFu;
+        }
+      }
+      if (!ok) return GzDone{0u, 0u, 0u};
+      if (late) {  // test hook: a wrong (later) start, the link kernel has to repair it
+        start = pos;
+        out_pos = flushed = 0;
+        ring_reset();
+      }
+    }
+    if (bad) {
+      flags |= bad;
+      break;
+    }
+    if (last) {  // the member's trailer (RFC 1952 §2.3), then another member or the stream's end
+      bs.drop(bs.cnt & 7u);
+      uint32_t at = (bs.next_word() * 32u - bs.cnt) / 8u;
+      if (at + 8u > nb) {
+        flags |= fin ? GZP_BAD : GZP_OVERRUN;
+        break;
+      }
+      if (n_ends == GZ_ENDS) {
+        flags |= GZP_ENDS;
+        break;
+      }
+      const uint32_t crc = gz_le32(a, at), isize = gz_le32(a, at + 4u);
+      if (lane == 0) {
+        pc->end_at[n_ends] = out_pos;
+        pc->end_crc[n_ends] = crc;
+        pc->end_isize[n_ends] = isize;
+      }
+      ++n_ends;
+      at += 8u;
+      pos = at * 8u;
+      if (at + 3u <= nb && uni(gz_byte(a, at) | gz_byte(a, at + 1u) << 8 | gz_byte(a, at + 2u) << 16) == 0x088b1fu) {
+        uint32_t why = 0;
+        const uint32_t p = uni(gz_header(reinterpret_cast<const uint8_t *>(a.comp), nb, fin, at, &why));
+        if (!p) {
+          flags |= uni(why);
+          break;
+        }
+        pos = p * 8u;
+        mstart = (int)out_pos;
+        bs.start(a.comp, p);
+      } else if (uni(gz_zeros(reinterpret_cast<const uint8_t *>(a.comp), nb, at) ? 1u : 0u)) {  // nothing more, or zeros: the end
+        flags |= GZP_EOS;
+        break;
+      } else {
+        flags |= (!fin && at + 3u > nb) ? GZP_OVERRUN : GZP_BAD;
+        break;
+      }
+    }
+    if (pos >= stop) break;
+  }
+done:
+  if ((out_pos & ~(GZ_FLUSH - 1u)) > flushed) flush_to(out_pos & ~(GZ_FLUSH - 1u));
+  flush_rest();
+  if (lane == 0) {
+    pc->start = start;
+    pc->end = pos;
+    pc->n_sym = out_pos;
+    pc->flags = flags;
+    pc->n_ends = n_ends;
+  }
+  return GzDone{uni(flags), uni(pos), uni(out_pos)};
+}
+
+// one wavefront per piece: its start (known, or searched), then its symbols
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ING_WAVES, 8))) gmx_gz_decode_kernel(GzArgs a) {
+  __shared__ WaveLds L;
+  const uint32_t i = blockIdx.x, lane = threadIdx.x & 63u;
+  if (i >= a.n_pieces || (!a.fresh && a.st->eos)) return;
+  if (i == 0) {
+    (void)gz_decode(L, a, 0, a.fresh ? 0u : a.st->bit, a.fresh != 0, false, false);
+    return;
+  }
+  const bool late = uni(a.late_mod && i % a.late_mod == 0 ? 1u : 0u) != 0, drop = uni(a.drop_mod && i % a.drop_mod == a.drop_mod - 1u ? 1u : 0u) != 0;
+  const uint32_t lo = uni(i * a.piece_bits), hi = uni(min((i + 1u) * a.piece_bits, a.n_own * 8u));
+  const uint32_t n_words = uni((a.n_bytes + 3u) / 4u);
+  for (uint32_t base = lo; base < hi && !drop; base += 64u) {
+    // the 17-bit screen at 64 positions: BFINAL 0, BTYPE 10b, HLIT <= 29, HDIST <= 29; then, lane by lane, the code-length
+    // code behind it must be complete (its HCLEN + 4 lengths of 3 bits: Kraft sum 1) — most chance positions fail here, before
+    // a trial decode costs the wave a table build
+    const uint32_t b = base + lane;
+    auto bits64 = [&](uint32_t at) {  // 64 bits of the chunk from bit `at`
+      const uint32_t wi = at >> 5, sh = at & 31u;
+      const uint64_t lo = (uint64_t)(wi + 1u < n_words ? a.comp[wi + 1u] : 0u) << 32 | (wi < n_words ? a.comp[wi] : 0u);
+      const uint64_t hi3 = wi + 2u < n_words ? a.comp[wi + 2u] : 0u;
+      return sh ? (lo >> sh) | (hi3 << (64u - sh)) : lo;
+    };
+    const uint64_t w = bits64(b);
+    bool pass = b < hi && (w & 7u) == 4u && ((w >> 3) & 31u) <= 29u && ((w >> 8) & 31u) <= 29u;
+    if (pass) {
+      const uint32_t hclen = (uint32_t)((w >> 13) & 15u) + 4u;
+      const uint64_t cl = bits64(b + 17u);
+      uint32_t kraft = 0;
+      for (uint32_t k = 0; k < hclen; ++k) {
+        const uint32_t l = (uint32_t)(cl >> (3u * k)) & 7u;
+        kraft += l ? 128u >> l : 0u;
+      }
+      pass = kraft == 128u;
+    }
+    unsigned long long m = __ballot(pass);
+    while (m) {
+      const uint32_t j = (uint32_t)__builtin_ctzll(m);
+      m &= m - 1ull;
+      if (uni(gz_decode(L, a, i, base + j, false, true, late).flags)) return;
+    }
+  }
+  if (lane == 0) {  // no start: the link kernel decodes this piece from where the one before ended
+    a.pieces[i].start = 0xFFFFFFFFu;
+    a.pieces[i].flags = 0;
+    a.pieces[i].n_sym = 0;
+    a.pieces[i].n_ends = 0;
+  }
+}
+
+// One wavefront: the chain of pieces in stream order, repairs included; the chunk's text offsets and length.
+__global__ void __launch_bounds__(64) gmx_gz_link_kernel(GzArgs a, uint64_t max_text) {
+  __shared__ WaveLds L;
+  const uint32_t lane = threadIdx.x & 63u;
+  GzState *const st = a.st;
+  if (a.fresh) {
+    if (lane == 0) {
+      st->eos = 0;
+      st->run_crc = 0xFFFFFFFFu;
+      st->run_len = 0;
+    }
+    __syncthreads();
+  }
+  uint32_t flags = 0, n_chain = 0, repairs = 0;
+  uint64_t text = 0;
+  if (!a.fresh && uni(st->eos)) {  // the stream ended in a chunk before: zeros only
+    if (!gz_zeros(reinterpret_cast<const uint8_t *>(a.comp), a.n_bytes, uni(st->bit) / 8u)) flags = GMX_INGEST_BAD_MEMBER;
+    if (lane == 0) st->bit = uni(st->bit) > a.n_own * 8u ? uni(st->bit) - a.n_own * 8u : 0u;
+  } else {
+    uint32_t prev_end = 0, pf = 0;
+    for (uint32_t i = 0; i < a.n_pieces; ++i) {
+      GzPiece *const pc = a.pieces + i;
+      GzDone d{uni(pc->flags), uni(pc->end), uni(pc->n_sym)};  // (written by gmx_gz_decode_kernel)
+      if (i > 0) {
+        if (prev_end >= gz_stop_bit(a, i)) {  // a block of the piece before reaches over this piece's span: nothing left here
+          d = GzDone{GZP_FOUND, prev_end, 0u};
+          if (lane == 0) {
+            pc->start = pc->end = prev_end;
+            pc->n_sym = pc->n_ends = 0;
+            pc->flags = GZP_FOUND;
+          }
+        } else if (!(d.flags & GZP_FOUND) || (d.flags & GZP_BAD) || uni(pc->start) != prev_end) {  // speculation that does not line up: decode it again
+          d = gz_decode(L, a, i, prev_end, false, false, false);
+          ++repairs;
+          if (d.flags & GZP_BAD) flags |= GMX_INGEST_GZ_UNREPAIRED;
+        }
+      }
+      pf = d.flags;
+      if (a.debug && lane == 0) printf("[gz] piece %u: flags %u start %u end %u n_sym %u (stop %u, prev_end %u)\n", i, pf, pc->start, d.end, d.n_sym, gz_stop_bit(a, i), prev_end);
+      if (pf & GZP_BAD) flags |= GMX_INGEST_BAD_MEMBER;
+      if (pf & GZP_CAPPED) flags |= GMX_INGEST_GZ_PIECE_BOUND;
+      if (pf & GZP_OVERRUN) flags |= a.final_chunk ? GMX_INGEST_BAD_MEMBER : GMX_INGEST_GZ_LOOKAHEAD;
+      if (pf & GZP_ENDS) flags |= GMX_INGEST_GZ_MEMBER_ENDS;
+      if (flags) break;
+      if (lane == 0) pc->text_off = (uint32_t)text;
+      text += d.n_sym;
+      prev_end = d.end;
+      n_chain = i + 1u;
+      if (pf & GZP_EOS) break;
+    }
+    if (!flags) {
+      if (pf & GZP_EOS) {
+        if (!a.final_chunk && lane == 0) {  // (the trailer may lie in the look-ahead: the next chunk's zeros start behind it)
+          st->eos = 1;
+          st->bit = prev_end > a.n_own * 8u ? prev_end - a.n_own * 8u : 0u;
+        }
+      } else if (a.final_chunk) {
+        flags = GMX_INGEST_BAD_MEMBER;  // the stream stops without its last member's trailer: truncated
+      } else if (lane == 0) {
+        st->bit = prev_end - a.n_own * 8u;
+      }
+      if (text > max_text) flags |= GMX_INGEST_GZ_TEXT_LIMIT;
+    }
+  }
+  if (lane == 0) {
+    st->flags = flags;
+    st->text_len = flags ? 0u : (uint32_t)text;
+    st->n_pieces = flags ? 0u : n_chain;
+    st->repairs += repairs;
+  }
+}
+
+// One block: the 32 KB in front of every piece (wins[i]), in stream order; the last 32 KB of the chunk's text for the next chunk.
+__global__ void __launch_bounds__(1024) gmx_gz_window_kernel(GzArgs a, uint8_t *wins, uint8_t *window) {
+  __shared__ uint8_t w[2][GZ_WIN];
+  const uint32_t t = threadIdx.x;
+  const GzState *st = a.st;
+  const uint32_t n = st->n_pieces;
+  if (st->flags || n == 0) return;
+  for (uint32_t k = t * 16u; k < GZ_WIN; k += 16u * blockDim.x) *reinterpret_cast<uint4 *>(&w[0][k]) = a.fresh ? make_uint4(0, 0, 0, 0) : *reinterpret_cast<const uint4 *>(window + k);
+  __syncthreads();
+  uint32_t cur = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint8_t *c = w[cur];
+    uint8_t *nx = w[cur ^ 1u];
+    for (uint32_t k = t * 16u; k < GZ_WIN; k += 16u * blockDim.x) *reinterpret_cast<uint4 *>(wins + (size_t)i * GZ_WIN + k) = *reinterpret_cast<const uint4 *>(c + k);
+    const uint32_t len = a.pieces[i].n_sym;
+    const uint16_t *s = a.sym + (size_t)i * a.cap;
+    for (uint32_t k = t; k < GZ_WIN; k += blockDim.x) {
+      const int q = (int)len - (int)GZ_WIN + (int)k;
+      uint32_t v;
+      if (q < 0) {
+        v = c[GZ_WIN + q];
+      } else {
+        v = s[q];
+        if (v >= 256u) v = c[v - 256u];
+      }
+      nx[k] = (uint8_t)v;
+    }
+    __syncthreads();
+    cur ^= 1u;
+  }
+  for (uint32_t k = t * 16u; k < GZ_WIN; k += 16u * blockDim.x) *reinterpret_cast<uint4 *>(window + k) = *reinterpret_cast<const uint4 *>(&w[cur][k]);
+}
+
+// symbols -> bytes: blockIdx.x the piece, blockIdx.y its share
+__global__ void __launch_bounds__(256) gmx_gz_resolve_kernel(GzArgs a, const uint8_t *wins, uint8_t *text) {
+  const uint32_t i = blockIdx.x;
+  const GzState *st = a.st;
+  if (st->flags || i >= st->n_pieces) return;
+  const uint32_t len = a.pieces[i].n_sym;
+  uint8_t *const dst = text + a.pieces[i].text_off;
+  const uint16_t *s = a.sym + (size_t)i * a.cap;
+  const uint8_t *win = wins + (size_t)i * GZ_WIN;
+  for (uint32_t q = blockIdx.y * blockDim.x + threadIdx.x; q < len; q += gridDim.y * blockDim.x) {
+    const uint32_t v = s[q];
+    dst[q] = v < 256u ? (uint8_t)v : win[v - 256u];
+  }
+}
+
+// one wavefront per piece: the CRC register (from 0) of its text between member ends, and x^(8 length) to move a register past it
+__global__ void __launch_bounds__(64) gmx_gz_crc_kernel(GzArgs a, const uint8_t *text) {
+  __shared__ uint32_t crc_tab[1024];
+  const uint32_t i = blockIdx.x, lane = threadIdx.x & 63u;
+  const GzState *st = a.st;
+  if (st->flags || i >= st->n_pieces) return;
+  GzPiece *const pc = a.pieces + i;
+  ing_crc_tables(crc_tab);
+  const uint32_t n_ends = uni(pc->n_ends), n_sym = uni(pc->n_sym), off = uni(pc->text_off);
+  for (uint32_t k = 0; k <= n_ends; ++k) {
+    const uint32_t lo = k ? uni(pc->end_at[k - 1u]) : 0u, hi = k < n_ends ? uni(pc->end_at[k]) : n_sym;
+    const uintptr_t p = (uintptr_t)(text + off + lo);
+    const uint32_t first = (uint32_t)(p & 15u);
+    const uint32_t c = ing_crc_wave(crc_tab, (const ing_g8 *)(p - first), first, first + (hi - lo), 0u);
+    const uint32_t pw = ing_xpow8(hi - lo);
+    if (lane == 0) {
+      pc->seg_crc[k] = c;
+      pc->seg_pow[k] = pw;
+    }
+  }
+}
+
+// one lane: the parts combined in stream order, every member's CRC-32 and ISIZE checked; the chunk's status for gmx_layout_kernel
+__global__ void __launch_bounds__(64) gmx_gz_check_kernel(GzArgs a, IngestInflateStatus *inf) {
+  if (threadIdx.x != 0) return;
+  GzState *const st = a.st;
+  uint32_t flags = st->flags;
+  if (!flags) {
+    uint32_t r = st->run_crc, len = st->run_len;
+    for (uint32_t i = 0; i < st->n_pieces && !flags; ++i) {
+      const GzPiece &pc = a.pieces[i];
+      for (uint32_t k = 0; k <= pc.n_ends; ++k) {
+        const uint32_t lo = k ? pc.end_at[k - 1u] : 0u, hi = k < pc.n_ends ? pc.end_at[k] : pc.n_sym;
+        r = ing_mulmod(r, pc.seg_pow[k]) ^ pc.seg_crc[k];
+        len += hi - lo;
+        if (k < pc.n_ends) {
+          if (~r != pc.end_crc[k] || len != pc.end_isize[k]) {
+            flags |= GMX_INGEST_BAD_CRC;
+            break;
+          }
+          r = 0xFFFFFFFFu;
+          len = 0;
+        }
+      }
+    }
+    st->run_crc = r;
+    st->run_len = len;
+    if (flags) {
+      st->flags = flags;
+      st->text_len = 0;
+    }
+  }
+  inf->flags = flags;
+  inf->bad_member = flags ? 0u : 0xFFFFFFFFu;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1116,6 +1736,15 @@ struct gmx_ingest {
   int check_crc = 1;
   uint32_t exp_mode = 0;
   unsigned long long *d_dbg = nullptr;  // GMX_INGEST_STATS=1: counters of gmx_inflate_kernel, printed by gmx_ingest_destroy
+  struct Gz {  // plain gzip (gmx_ingest_submit_gzip): allocated by the first such chunk; used on `stream` only, chunk after chunk
+    GzPiece *d_pieces = nullptr;
+    uint16_t *d_sym = nullptr;       // max_pieces * cap symbols
+    uint8_t *d_wins = nullptr;       // the 32 KB in front of each piece
+    uint8_t *d_window = nullptr;     // the last 32 KB of the chunk before
+    GzState *d_state = nullptr;
+    uint32_t piece_bytes = 0, max_pieces = 0, cap = 0, late_mod = 0, drop_mod = 0;
+  } *gz = nullptr;
+  bool gz_fresh = true;  // the next gzip chunk starts a file
 };
 
 namespace {
@@ -1231,6 +1860,7 @@ void gmx_ingest_destroy(gmx_ingest *g) try {
     }
   }
   for (void *p : g->allocs) (void)hipFree(p);
+  delete g->gz;
   if (g->stream) (void)hipStreamDestroy(g->stream);
   if (g->copy_stream) (void)hipStreamDestroy(g->copy_stream);
   (void)hipGetLastError();
@@ -1247,6 +1877,7 @@ int gmx_ingest_reset(gmx_ingest *g) try {  // the next chunk starts a file: noth
     return GMX_EINVAL;
   }
   g->last_slot = -1;
+  g->gz_fresh = true;
   return GMX_OK;
 } GMX_GUARD_INT("gmx_ingest_reset")
 
@@ -1273,7 +1904,10 @@ static int ing_enqueue_inflate(gmx_ingest *g, int si, uint32_t n_members) {
   return GMX_OK;
 }
 // host_tail = ~0: the cut record comes from the chunk before on this device (g->last_slot); else that many bytes lie in front of the text
-static int ing_enqueue_scan(gmx_ingest *g, int si, uint32_t members_text, int final_chunk, bool inflate, uint32_t n_members, uint32_t host_tail = 0xFFFFFFFFu) {
+// gz_len: a plain gzip chunk, whose text length the device holds (members_text is then ignored; the newline kernels get a grid
+// for max_text, the tiles beyond the text leave at once)
+static int ing_enqueue_scan(gmx_ingest *g, int si, uint32_t members_text, int final_chunk, bool inflate, uint32_t n_members, uint32_t host_tail = 0xFFFFFFFFu,
+                            const uint32_t *gz_len = nullptr) {
   gmx_ingest::Slot &s = g->slot[si];
   const bool from_device = host_tail == 0xFFFFFFFFu;
   gmx_ingest::Slot *prev = from_device && g->last_slot >= 0 ? &g->slot[g->last_slot] : nullptr;
@@ -1281,8 +1915,12 @@ static int ing_enqueue_scan(gmx_ingest *g, int si, uint32_t members_text, int fi
     int rc = ing_enqueue_inflate(g, si, n_members);
     if (rc) return rc;
   }
-  hipLaunchKernelGGL(gmx_carry_kernel, dim3(64), dim3(256), 0, g->stream, prev ? prev->d_state : nullptr, prev ? prev->d_text : nullptr, s.d_state, s.d_text,
-                     members_text, (uint32_t)(final_chunk ? 1 : 0), from_device ? 0u : host_tail);
+  if (gz_len)
+    hipLaunchKernelGGL(gmx_carry_gz_kernel, dim3(64), dim3(256), 0, g->stream, prev ? prev->d_state : nullptr, prev ? prev->d_text : nullptr, s.d_state, s.d_text,
+                       gz_len, (uint32_t)(final_chunk ? 1 : 0));
+  else
+    hipLaunchKernelGGL(gmx_carry_kernel, dim3(64), dim3(256), 0, g->stream, prev ? prev->d_state : nullptr, prev ? prev->d_text : nullptr, s.d_state, s.d_text,
+                       members_text, (uint32_t)(final_chunk ? 1 : 0), from_device ? 0u : host_tail);
   ING_TRY(hipEventRecord(s.carried, g->stream));
   s.has_carried = true;
   if (prev) {  // (the slot of the chunk before may be overwritten once this kernel has read its end: ing_begin)
@@ -1290,7 +1928,7 @@ static int ing_enqueue_scan(gmx_ingest *g, int si, uint32_t members_text, int fi
     prev->has_follower = true;
   }
   ING_TRY(hipStreamWaitEvent(g->stream, inflate ? s.inflated : s.copied, 0));
-  const uint32_t n_tiles = (uint32_t)((ING_CARRY_MAX + (uint64_t)members_text + ING_TILE - 1) / ING_TILE);
+  const uint32_t n_tiles = gz_len ? g->n_tiles_max : (uint32_t)((ING_CARRY_MAX + (uint64_t)members_text + ING_TILE - 1) / ING_TILE);
   hipLaunchKernelGGL(gmx_nl_count_kernel, dim3(n_tiles), dim3(256), 0, g->stream, s.d_text, s.d_state, s.d_tiles);
   const uint32_t n_tile_blk = (n_tiles + ING_SCAN_BLOCK - 1) / ING_SCAN_BLOCK;
   hipLaunchKernelGGL(gmx_tile_scan1_kernel, dim3(n_tile_blk), dim3(64), 0, g->stream, s.d_tiles, n_tiles, s.d_tile_blk);
@@ -1298,7 +1936,7 @@ static int ing_enqueue_scan(gmx_ingest *g, int si, uint32_t members_text, int fi
   hipLaunchKernelGGL(gmx_nl_mark_kernel, dim3(n_tiles), dim3(256), 0, g->stream, s.d_text, s.d_state, s.d_tiles, s.d_tile_blk, s.d_line_end, g->cap_lines);
   hipLaunchKernelGGL(gmx_records_kernel, dim3(2048), dim3(256), 0, g->stream, s.d_text, s.d_state, s.d_line_end, s.d_rec_start, s.d_rec_len, s.d_skip, g->cap_reads);
   const uint32_t n_off_blk = (uint32_t)((g->cap_reads + ING_SCAN_BLOCK - 1) / ING_SCAN_BLOCK);  // (the chunk's read count is on the device: blocks beyond it leave at once)
-  hipLaunchKernelGGL(gmx_layout_kernel, dim3(1), dim3(64), 0, g->stream, s.d_state, inflate ? s.d_inflate_status : nullptr);
+  hipLaunchKernelGGL(gmx_layout_kernel, dim3(1), dim3(64), 0, g->stream, s.d_state, inflate || gz_len ? s.d_inflate_status : nullptr);
   hipLaunchKernelGGL(gmx_offsets1_kernel, dim3(n_off_blk), dim3(64), 0, g->stream, s.d_state, s.d_rec_len, s.d_offsets, s.d_off_blk);
   hipLaunchKernelGGL(gmx_offsets2_kernel, dim3(1), dim3(64), 0, g->stream, s.d_state, s.d_offsets, s.d_off_blk);
   hipLaunchKernelGGL(gmx_offsets3_kernel, dim3(n_off_blk), dim3(64), 0, g->stream, s.d_state, s.d_offsets, s.d_off_blk);
@@ -1393,6 +2031,103 @@ int gmx_ingest_submit_text(gmx_ingest *g, int slot, const uint8_t *text, uint64_
   ING_TRY(hipEventRecord(s.copied, g->copy_stream));
   return ing_enqueue_scan(g, slot, (uint32_t)n_bytes, final_chunk, false, 0);
 } GMX_GUARD_INT("gmx_ingest_submit_text")
+
+// The buffers of the gzip route: at its first chunk, and again when a chunk has more pieces than they were made for (the old
+// ones are freed: everything that used them ran on `stream`). Piece size GMX_GZ_PIECE (bytes; tests cut small files into many).
+static int ing_gz_alloc(gmx_ingest *g, uint32_t n_pieces) {
+  std::unique_ptr<gmx_ingest::Gz> z(new gmx_ingest::Gz());
+  uint64_t piece = 32u << 10;
+  if (const char *e = getenv("GMX_GZ_PIECE")) piece = std::min<uint64_t>(std::max<uint64_t>(64, (uint64_t)atoll(e)), 64u << 20);
+  z->piece_bytes = (uint32_t)piece;
+  z->max_pieces = std::max<uint32_t>(n_pieces, 4);
+  // symbols a piece may write: its blocks and the one that reaches over its end (a zlib block holds up to 16 K symbols: 1 M symbols
+  // is 64 bytes per symbol — FASTQ of one quality value inflates to less); beyond it GMX_INGEST_GZ_PIECE_BOUND
+  z->cap = (uint32_t)((std::max<uint64_t>(piece * 32u, 1u << 20) + GZ_FLUSH - 1) / GZ_FLUSH * GZ_FLUSH);
+  if (const char *e = getenv("GMX_GZ_TEST_FIND")) {  // test hook: "L,D" (gmx_gz_decode_kernel)
+    z->late_mod = (uint32_t)atoi(e);
+    if (const char *c = strchr(e, ',')) z->drop_mod = (uint32_t)atoi(c + 1);
+  }
+  g->allocs.reserve(g->allocs.size() + 8);
+  if (g->gz) {  // (the window and the stream state go on)
+    ING_TRY(hipStreamSynchronize(g->stream));
+    for (void *p : {(void *)g->gz->d_pieces, (void *)g->gz->d_sym, (void *)g->gz->d_wins}) {
+      g->allocs.erase(std::remove(g->allocs.begin(), g->allocs.end(), p), g->allocs.end());
+      (void)hipFree(p);
+    }
+    z->d_window = g->gz->d_window;
+    z->d_state = g->gz->d_state;
+    delete g->gz;
+    g->gz = nullptr;
+  }
+  int rc;
+  if ((rc = ing_alloc(g, &z->d_pieces, z->max_pieces, true)) || (rc = ing_alloc(g, &z->d_sym, (size_t)z->max_pieces * z->cap + 64, false)) ||
+      (rc = ing_alloc(g, &z->d_wins, (size_t)z->max_pieces * GZ_WIN, false)) || (!z->d_window && (rc = ing_alloc(g, &z->d_window, GZ_WIN, true))) ||
+      (!z->d_state && (rc = ing_alloc(g, &z->d_state, 1, true))))
+    return rc;
+  g->gz = z.release();
+  return GMX_OK;
+}
+
+int gmx_ingest_submit_gzip(gmx_ingest *g, int slot, const uint8_t *bytes, uint64_t n_bytes, uint64_t n_own, int final_chunk) try {
+  int rc = ing_begin(g, slot, "gmx_ingest_submit_gzip");
+  if (rc) return rc;
+  if ((!bytes && n_bytes) || n_own > n_bytes || n_bytes > g->max_comp || n_bytes >= (1u << 29) || (final_chunk && n_bytes != n_own)) {
+    gmx_set_error("gmx_ingest_submit_gzip: null bytes, n_own > n_bytes, look-ahead given with the final chunk, or more bytes than "
+                  "gmx_ingest_max_compressed() / 512 MB");
+    return GMX_EINVAL;
+  }
+  {
+    uint64_t piece = 32u << 10;  // (as ing_gz_alloc)
+    if (g->gz) piece = g->gz->piece_bytes;
+    else if (const char *e = getenv("GMX_GZ_PIECE")) piece = std::min<uint64_t>(std::max<uint64_t>(64, (uint64_t)atoll(e)), 64u << 20);
+    const uint32_t need = (uint32_t)std::max<uint64_t>(1, (n_own + piece - 1) / piece);
+    if ((!g->gz || g->gz->max_pieces < need) && (rc = ing_gz_alloc(g, need))) return rc;
+  }
+  gmx_ingest::Gz &z = *g->gz;
+  gmx_ingest::Slot &s = g->slot[slot];
+  if (n_bytes) ING_TRY(hipMemcpyAsync(s.d_comp, bytes, n_bytes, hipMemcpyHostToDevice, g->copy_stream));
+  ING_TRY(hipMemsetAsync(reinterpret_cast<uint8_t *>(s.d_comp) + n_bytes, 0, 16, g->copy_stream));  // (the bit reader's words behind the bytes)
+  ING_TRY(hipEventRecord(s.copied, g->copy_stream));
+  ING_TRY(hipStreamWaitEvent(g->stream, s.copied, 0));
+  GzArgs a;
+  a.comp = s.d_comp;
+  a.n_bytes = (uint32_t)n_bytes;
+  a.n_own = (uint32_t)n_own;
+  a.final_chunk = final_chunk ? 1u : 0u;
+  a.fresh = g->gz_fresh ? 1u : 0u;
+  a.piece_bits = z.piece_bytes * 8u;
+  a.n_pieces = (uint32_t)std::max<uint64_t>(1, (n_own + z.piece_bytes - 1) / z.piece_bytes);
+  a.cap = z.cap;
+  a.sym = z.d_sym;
+  a.pieces = z.d_pieces;
+  a.st = z.d_state;
+  a.debug = getenv("GMX_GZ_DEBUG") ? 1u : 0u;
+  a.late_mod = z.late_mod;
+  a.drop_mod = z.drop_mod;
+  uint8_t *const text = s.d_text + ING_CARRY_MAX;
+  hipLaunchKernelGGL(gmx_gz_decode_kernel, dim3(a.n_pieces), dim3(64), 0, g->stream, a);
+  hipLaunchKernelGGL(gmx_gz_link_kernel, dim3(1), dim3(64), 0, g->stream, a, (uint64_t)g->max_text);
+  hipLaunchKernelGGL(gmx_gz_window_kernel, dim3(1), dim3(1024), 0, g->stream, a, z.d_wins, z.d_window);
+  hipLaunchKernelGGL(gmx_gz_resolve_kernel, dim3(a.n_pieces, 16), dim3(256), 0, g->stream, a, (const uint8_t *)z.d_wins, text);
+  hipLaunchKernelGGL(gmx_gz_crc_kernel, dim3(a.n_pieces), dim3(64), 0, g->stream, a, (const uint8_t *)text);
+  hipLaunchKernelGGL(gmx_gz_check_kernel, dim3(1), dim3(64), 0, g->stream, a, s.d_inflate_status);
+  ING_TRY(hipGetLastError());
+  g->gz_fresh = false;
+  return ing_enqueue_scan(g, slot, 0, final_chunk, false, 0, 0xFFFFFFFFu, &z.d_state->text_len);
+} GMX_GUARD_INT("gmx_ingest_submit_gzip")
+
+int64_t gmx_ingest_gzip_repairs(gmx_ingest *g) try {
+  if (!g) {
+    gmx_set_error("null ingest");
+    return GMX_EINVAL;
+  }
+  if (!g->gz) return 0;
+  ING_TRY(hipSetDevice(g->device));
+  ING_TRY(hipStreamSynchronize(g->stream));
+  uint32_t v = 0;
+  ING_TRY(hipMemcpy(&v, &g->gz->d_state->repairs, 4, hipMemcpyDeviceToHost));
+  return (int64_t)v;
+} GMX_GUARD_INT("gmx_ingest_gzip_repairs")
 
 // Chunks dealt over several devices (one ingest per device): the cut record at a chunk's start lies on ANOTHER device, so a chunk
 // is uploaded and inflated at once (_deferred) and scanned (gmx_ingest_scan) when the caller has the end of the chunk before —

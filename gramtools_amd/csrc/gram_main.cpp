@@ -1401,6 +1401,87 @@ int ingest_text_file(const std::string &path, int threads, int device, OnChunk o
   return 0;
 }
 
+// A PLAIN gzip file (one deflate stream per member: gzip, pigz, ENA / SRA downloads) decoded on the device
+// (gmx_ingest_submit_gzip): chunks of GMX_GZ_CHUNK compressed bytes (default 32 MB) with 1 MB of the file behind
+// each as look-ahead, read into page-locked buffers and submitted with two chunks on the device. One engine only: the deflate
+// stream's window and position live in that engine's ingest. Return values as ingest_bgzf_file (1: not gzip).
+static uint64_t device_feed_gz_chunk() {
+  uint64_t c = 32ull << 20;
+  if (const char *e = getenv("GMX_GZ_CHUNK")) c = std::max<uint64_t>(64, (uint64_t)atoll(e));
+  return std::min<uint64_t>(c, 256ull << 20);
+}
+static bool looks_like_gzip(const std::string &path, uint64_t *size_out) {
+  const int fd = open(path.c_str(), O_RDONLY);
+  if (fd < 0) return false;
+  struct stat sb;
+  unsigned char h[3] = {0, 0, 0};
+  const bool ok = fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size >= 18 && pread(fd, h, 3, 0) == 3 && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8;
+  close(fd);
+  if (ok && size_out) *size_out = (uint64_t)sb.st_size;
+  return ok;
+}
+
+template <class OnChunk>
+int ingest_gzip_file(const std::string &path, int threads, int device, OnChunk on_chunk, uint64_t *delivered) {
+  *delivered = 0;
+  uint64_t size = 0;
+  if (!looks_like_gzip(path, &size)) return 1;
+  FdCloser f{open(path.c_str(), O_RDONLY)};
+  if (f.fd < 0) return 1;
+  const uint64_t chunk = std::min<uint64_t>(device_feed_gz_chunk(), size), look = 1u << 20;
+  DeviceFeed &df = g_device_feed;
+  // text room for 8:1 (FASTQ compresses 3-5 fold; a chunk that inflates further comes back with GMX_INGEST_GZ_TEXT_LIMIT)
+  device_feed_prepare(device, std::max<uint64_t>(2 * (chunk + look), std::min<uint64_t>(8 * chunk, 3ull << 30)), chunk + look + 64);
+  if (!df.ing || gmx_ingest_max_compressed(df.ing) < chunk + look) return 1;
+  gmx_ingest *ing = df.ing;
+  GMX_CHECK(gmx_ingest_reset(ing));
+  const unsigned T = (unsigned)std::max(1, std::min(threads, 64));
+  const size_t n_chunks = (size_t)((size + chunk - 1) / chunk);
+  auto fail_chunk = [&]() -> size_t {
+    const char *tf = getenv("GMX_INGEST_TEST_FAIL_CHUNK");  // test hook: the device decoder "gives up" on this chunk
+    return tf ? (size_t)atoll(tf) : ~(size_t)0;
+  };
+  size_t n_submitted = 0;
+  auto submit = [&]() -> bool {
+    const size_t ci = n_submitted;
+    const uint64_t at = (uint64_t)ci * chunk, own = std::min<uint64_t>(chunk, size - at);
+    const bool final_chunk = ci + 1 == n_chunks;
+    const uint64_t n = final_chunk ? own : std::min<uint64_t>(own + look, size - at);
+    const double t_read = now_s();
+    if (!pread_parallel(f.fd, at, df.stage[ci % 3].data(), (size_t)n, T)) return false;
+    g_feed.read_s += now_s() - t_read;
+    GMX_CHECK(gmx_ingest_submit_gzip(ing, (int)(ci % 3), df.stage[ci % 3].data(), n, own, final_chunk ? 1 : 0));
+    ++n_submitted;
+    feed_trace("gzip chunk submitted to the device");
+    return true;
+  };
+  auto drain = [&](size_t from) {
+    for (size_t cj = from; cj < n_submitted; ++cj) {
+      gmx_ingest_result drop;
+      (void)gmx_ingest_wait(ing, (int)(cj % 3), &drop);
+    }
+  };
+  for (size_t ci = 0; ci < n_chunks; ++ci) {
+    while (n_submitted < std::min(n_chunks, ci + 2)) {  // this chunk and the one behind it on the device
+      if (!submit()) {
+        drain(ci);
+        return *delivered == 0 ? 1 : 2;
+      }
+    }
+    gmx_ingest_result res;
+    GMX_CHECK(gmx_ingest_wait(ing, (int)(ci % 3), &res));
+    feed_trace("gzip chunk decoded, scanned and packed");
+    if (ci == fail_chunk()) res.status |= GMX_INGEST_BAD_MEMBER;
+    if (res.status) {
+      drain(ci + 1);
+      return 2;  // (gave up, also on its first chunk: the host reader takes the file over and reports real damage itself)
+    }
+    on_chunk(res, (int)(ci % 3));
+    *delivered += res.n_reads;
+  }
+  return 0;
+}
+
 // Several engines: the chunks dealt round, each uploaded to its device at once (gmx_ingest_submit_text_deferred, two per device
 // ahead), scanned in file order with the cut record of the chunk before handed over through the host — as ingest_bgzf_file_dealt.
 template <class OnChunk>
@@ -1610,6 +1691,7 @@ int run_parse_check(const std::string &path, int threads) {
       collect(blk);
     };
     int rc = ingest_bgzf_file(path, threads, 0, take, &delivered);
+    if (rc == 1 && delivered == 0) rc = ingest_gzip_file(path, threads, 0, take, &delivered);  // (plain gzip: pieces decoded side by side)
     if (rc == 1 && delivered == 0) rc = ingest_text_file(path, threads, 0, take, &delivered);  // (not BGZF: plain text through the same kernels)
     if (rc == 0)
       std::cout << "device " << fast.offsets.size() - 1 << " " << fast.bases.size() << " " << fnv(fast) << std::endl;
@@ -2027,8 +2109,12 @@ int run_genotype(const Args &a) {
       };
       int rc = dealt ? ingest_bgzf_file_dealt(path, max_threads, devices, map_chunk, &delivered)
                      : ingest_bgzf_file(path, max_threads, devices[0], [&](const gmx_ingest_result &res, int slot) { map_chunk(res, 0, slot); }, &delivered);
+      // plain gzip, one engine: decoded on the device too, at any --max_threads (the host's inflation is the
+      // slower at every thread count); several engines keep the host reader (the stream's window would travel through the host)
+      const bool gz_route = rc == 1 && delivered == 0 && devices.size() == 1 && looks_like_gzip(path, nullptr);
+      if (gz_route) rc = ingest_gzip_file(path, max_threads, devices[0], [&](const gmx_ingest_result &res, int slot) { map_chunk(res, 0, slot); }, &delivered);
       // not BGZF: plain four-line FASTQ takes the same route minus the inflate kernel (round 6; GMX_HOST_FASTQ=1: the host parser)
-      const bool text_route = rc == 1 && delivered == 0 && plain_fastq_on_device(max_threads, devices.size());
+      const bool text_route = rc == 1 && delivered == 0 && !gz_route && plain_fastq_on_device(max_threads, devices.size());
       if (text_route)
         rc = dealt ? ingest_text_file_dealt(path, max_threads, devices, map_chunk, &delivered)
                    : ingest_text_file(path, max_threads, devices[0], [&](const gmx_ingest_result &res, int slot) { map_chunk(res, 0, slot); }, &delivered);
@@ -2042,7 +2128,7 @@ int run_genotype(const Args &a) {
       }
       if (rc == 2) {
         sync_all();
-        std::cerr << "warning: " << path << ": the device-side " << (text_route ? "FASTQ scanner" : "BGZF decoder") << " gave up after " << delivered << " reads; the host reader takes over" << std::endl;
+        std::cerr << "warning: " << path << ": the device-side " << (text_route ? "FASTQ scanner" : gz_route ? "gzip decoder" : "BGZF decoder") << " gave up after " << delivered << " reads; the host reader takes over" << std::endl;
         skip_reads = delivered;
         in_file = 0;               // (the host reader counts the file's reads from its start again)
         total_reads -= delivered;

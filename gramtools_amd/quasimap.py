@@ -695,7 +695,7 @@ def bgzf_members(data) -> list:
 
 class Ingest:
     """Reads files decoded on the device (include/gmx.h, gmx_ingest_*): BGZF members inflated, four-line records found and
-    packed into bit planes by HIP kernels; three slots (0, 1, 2) taken in turn. ``submit_bgzf`` / ``submit_text`` enqueue a chunk, ``wait`` returns
+    packed into bit planes by HIP kernels; three slots (0, 1, 2) taken in turn. ``submit_bgzf`` / ``submit_text`` / ``submit_gzip`` enqueue a chunk, ``wait`` returns
     its gmx_ingest_result; Quasimapper.map_ingested maps what a slot holds."""
 
     def __init__(self, device: int = 0, max_text_bytes: int = 64 << 20):
@@ -763,6 +763,20 @@ class Ingest:
         buf = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else text
         self._keep[slot] = (buf,)
         check(self.lib.gmx_ingest_submit_text(self.h, slot, buf.ctypes.data if buf.size else None, buf.size, 1 if final else 0))
+
+    def submit_gzip(self, slot: int, data, n_own: int, final: bool):
+        """A chunk of a PLAIN gzip file (gmx_ingest_submit_gzip): data[:n_own] is the chunk's share of the file, data[n_own:] the
+        file's bytes behind it (look-ahead; none with the final chunk). Chunks of one file in order, alternating slots."""
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+        self._keep[slot] = (buf,)
+        check(self.lib.gmx_ingest_submit_gzip(self.h, slot, buf.ctypes.data if buf.size else None, buf.size, n_own, 1 if final else 0))
+
+    def gzip_repairs(self) -> int:
+        """Test hook: pieces of gzip chunks decoded again from where the piece before really ended (since the ingest was created)."""
+        n = self.lib.gmx_ingest_gzip_repairs(self.h)
+        if n < 0:
+            check(int(n))
+        return int(n)
 
     def wait(self, slot: int) -> "_lib.IngestResult":
         res = _lib.IngestResult()

@@ -241,6 +241,12 @@ typedef struct {
 #define GMX_INGEST_BAD_MEMBER 2u      /* a member's deflate data could not be decoded */
 #define GMX_INGEST_BAD_CRC 4u         /* a member's text does not match its trailer */
 #define GMX_INGEST_TOO_MANY_LINES 8u  /* more lines / records than the ingest has room for (lines of a few bytes) */
+/* plain gzip only (gmx_ingest_submit_gzip): */
+#define GMX_INGEST_GZ_UNREPAIRED 16u   /* a piece whose speculative start did not line up could not be decoded from its predecessor's end */
+#define GMX_INGEST_GZ_LOOKAHEAD 32u    /* the chunk's last block does not end inside the look-ahead bytes given */
+#define GMX_INGEST_GZ_PIECE_BOUND 64u  /* a piece inflates to more than its output bound (streams of 1000:1 and the like) */
+#define GMX_INGEST_GZ_MEMBER_ENDS 128u /* more member ends inside one piece than it can record (members of a few bytes) */
+#define GMX_INGEST_GZ_TEXT_LIMIT 256u  /* the chunk's text is larger than the ingest's max_text_bytes */
 typedef struct {
   uint32_t status;        /* 0, or GMX_INGEST_* bits: the reads below are then NOT to be used */
   uint32_t bad_member;    /* first member (index within the chunk) with GMX_INGEST_BAD_MEMBER / _BAD_CRC */
@@ -264,6 +270,17 @@ int gmx_ingest_reset(gmx_ingest *g); /* the next chunk is a file's first: nothin
 int gmx_ingest_submit_bgzf(gmx_ingest *g, int slot, const uint8_t *compressed, uint64_t n_bytes, const gmx_bgzf_member *members,
                            uint64_t n_members, int final_chunk);
 int gmx_ingest_submit_text(gmx_ingest *g, int slot, const uint8_t *text, uint64_t n_bytes, int final_chunk);
+/* PLAIN gzip (gzip, pigz, ENA / SRA downloads: one deflate stream per member, members concatenated) decoded on the device,
+ * DESIGN.md §11.2. A file's bytes go to ONE ingest in order, in chunks of any size, alternating slots as for _submit_text:
+ * [0, n_own) is this chunk's share of the file, [n_own, n_bytes) look-ahead (the file's bytes behind it) that only the decoding
+ * of the chunk's last deflate block may read — a block that does not end inside it: GMX_INGEST_GZ_LOOKAHEAD. The final chunk has
+ * none (n_bytes = n_own). The chunk is cut into pieces of GMX_GZ_PIECE bytes (default 32 KB) decoded side by side from
+ * speculative block starts; a start that does not line up is repaired on the device. The stream position, the last 32 KB of
+ * text and the open member's CRC travel to the next chunk inside the ingest (gmx_ingest_reset: a new file). Every member's
+ * CRC-32 and ISIZE are checked (GMX_INGEST_BAD_CRC); damaged deflate data or a truncated stream: GMX_INGEST_BAD_MEMBER. Zero
+ * bytes behind the last member are accepted. n_bytes <= min(gmx_ingest_max_compressed(), 2^29). */
+int gmx_ingest_submit_gzip(gmx_ingest *g, int slot, const uint8_t *bytes, uint64_t n_bytes, uint64_t n_own, int final_chunk);
+int64_t gmx_ingest_gzip_repairs(gmx_ingest *g); /* test hook: pieces decoded again from their predecessor's end, since creation */
 int gmx_ingest_wait(gmx_ingest *g, int slot, gmx_ingest_result *out);
 /* A file's chunks dealt over SEVERAL devices (one gmx_ingest each; SURVEY.md §8e: the path shards by chunk): the record cut by a
  * chunk's end continues on another device, so the caller carries it through the host. _deferred uploads a chunk and enqueues its
