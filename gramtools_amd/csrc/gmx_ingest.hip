@@ -14,6 +14,8 @@
 //   gmx_records_kernel     four-line records: checks '@' / '+' / equal lengths, read lengths, one length for all or not
 //   gmx_fq_pack_kernel     32 letters -> one pair of bit planes, in the layout gmx_pack_reads / the host parser produce
 //                          (include/gmx.h), unencodable reads flagged in skip[] (encode_dna_bases, common/utils.cpp:73-92)
+//   gmx_seq_lines1-3 / gmx_seq_records / gmx_seq_pack   FASTA and one-read-per-line text (gmx_ingest_set_format) in place of
+//                          gmx_records / gmx_fq_pack: see "records whose sequence is not one line" below
 //
 // A chunk's incomplete last record is carried into the next chunk on the device. Anything irregular (not four-line FASTQ, a
 // damaged member, a CRC mismatch) is reported in gmx_ingest_result::status and decided by the caller (`gram` re-inflates the
@@ -61,7 +63,7 @@ struct IngestState {
   unsigned long long n_pairs;
   unsigned long long sub_pairs[16];  // pair index of read i * 2^20 (offsets form): where a launch of <= 2^20 reads starts
   uint32_t final_chunk;
-  uint32_t pad;
+  uint32_t n_heads;        // FASTA / LINES: lines that start a record (gmx_seq_lines2_kernel)
 };
 
 struct IngestInflateStatus {  // written by gmx_inflate_kernel (a stream of its own), merged into the chunk's state by gmx_layout_kernel
@@ -1119,6 +1121,211 @@ __global__ void __launch_bounds__(256) gmx_fq_pack_kernel(const uint8_t *text, I
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// records whose sequence is not one line: FASTA and one-read-per-line text (gmx_ingest_set_format; the rules are those of
+// `gram`'s general host reader, SeqReader::next). Behind the same newline kernels:
+//   gmx_seq_lines1_kernel   every line classified — does it start a record (a head), how many bases does it add (its bytes minus
+//                           the '\n' and ONE '\r' in front of it; a FASTA header adds none) — and both numbers scanned within
+//                           blocks of 1024 lines as one 64-bit sum (heads << 32 | bases: a chunk's text stays below 2^32 bytes);
+//                           one wavefront per block, no LDS, as the tile scans above
+//   gmx_seq_lines2_kernel   the blocks' sums scanned (one wavefront): heads and bases of the chunk, hence its read count
+//   gmx_seq_lines3_kernel   line i: bases of the chunk in front of it -> line_base[i]; a head writes its line into rec_line[record]
+//   gmx_seq_records_kernel  record r: lines [rec_line[r], rec_line[r + 1]), length = difference of their line_base; where the text
+//                           of a record that lies in ONE line starts (ING_MULTI: it does not); what the chunk's records consume
+//   gmx_seq_pack_kernel     gmx_fq_pack_kernel, plus: base 32 w of a record of several lines is found by a binary search over the
+//                           record's own lines in line_base, and up to 32 letters are gathered across line ends from there
+// FASTA: a head is a line whose first byte is '>'; a record is complete when the next head has been seen or the file ends, so a
+// chunk consumes up to its LAST head and carries the rest. LINES: a head is a non-empty line and holds its record.
+// ------------------------------------------------------------------------------------------------------------------
+#define ING_MULTI 0xFFFFFFFFu   // rec_start[r]: the record's bases lie in several lines (a text offset stays below 3 GB + 1 MB + 64)
+#define ING_HEAD 0x8000u        // line_rec[i]: the line starts a record (the low bits: records started in front of it within its block)
+
+__device__ __forceinline__ uint32_t ing_seq_lines(const IngestState *st, const uint32_t *line_end) {  // lines of the chunk, as gmx_records_kernel counts them
+  const uint32_t lo = st->text_start, hi = lo + st->text_len, n_nl = st->n_lines;
+  const uint32_t last_nl_end = n_nl ? line_end[n_nl - 1] + 1u : lo;
+  return n_nl + (st->final_chunk && last_nl_end < hi ? 1u : 0u);
+}
+__device__ __forceinline__ uint32_t ing_seq_line_start(const uint32_t *line_end, uint32_t i, uint32_t lo) { return i ? line_end[i - 1u] + 1u : lo; }
+
+__global__ void __launch_bounds__(64) gmx_seq_lines1_kernel(const uint8_t *text, IngestState *st, const uint32_t *line_end, uint32_t format, uint16_t *line_rec,
+                                                            uint32_t *line_base, unsigned long long *blk_tot) {
+  if (st->flags & GMX_INGEST_TOO_MANY_LINES) return;
+  const uint32_t lines = ing_seq_lines(st, line_end);
+  if (blockIdx.x * ING_SCAN_BLOCK >= lines) return;
+  const uint32_t lo = st->text_start, hi = lo + st->text_len, n_nl = st->n_lines;
+  const uint32_t lane = threadIdx.x & 63u, base = blockIdx.x * ING_SCAN_BLOCK + lane * 16u;
+  unsigned long long v[16], sum = 0;
+  bool bad = false;
+  uint32_t s = base < lines ? ing_seq_line_start(line_end, base, lo) : 0u;
+#pragma unroll
+  for (uint32_t j = 0; j < 16u; ++j) {
+    v[j] = 0;
+    if (base + j < lines) {
+      const uint32_t e = base + j < n_nl ? line_end[base + j] : hi;
+      uint32_t n = e - s;
+      const uint32_t first = n ? text[s] : 0u;
+      if (n && text[e - 1u] == '\r') --n;
+      if (format == GMX_INGEST_FORMAT_FASTA) {
+        v[j] = first == '>' ? 1ull << 32 : (unsigned long long)n;
+      } else if (n) {
+        v[j] = (1ull << 32) | n;
+        bad = bad || first == '@' || first == '>';  // (the host reader changes format there)
+      }
+      s = e + 1u;
+    }
+    sum += v[j];
+  }
+  unsigned long long incl = sum;
+  for (int d = 1; d < 64; d <<= 1) {
+    const unsigned long long up = __shfl_up(incl, d);
+    if ((int)lane >= d) incl += up;
+  }
+  unsigned long long run = incl - sum;
+#pragma unroll
+  for (uint32_t j = 0; j < 16u; ++j) {
+    if (base + j < lines) {
+      line_rec[base + j] = (uint16_t)((uint32_t)(run >> 32) | (v[j] >> 32 ? ING_HEAD : 0u));
+      line_base[base + j] = (uint32_t)run;
+    }
+    run += v[j];
+  }
+  if (lane == 63u) blk_tot[blockIdx.x] = incl;
+  const unsigned long long any_bad = __ballot(bad);
+  if (lane == 0 && any_bad) atomicOr(&st->flags, GMX_INGEST_BAD_RECORD);
+}
+__global__ void __launch_bounds__(64) gmx_seq_lines2_kernel(IngestState *st, const uint32_t *line_end, uint32_t format, unsigned long long *blk_tot, uint32_t *line_base,
+                                                            uint32_t *rec_line, uint32_t cap_reads) {
+  if (st->flags & GMX_INGEST_TOO_MANY_LINES) return;
+  const uint32_t lines = ing_seq_lines(st, line_end);
+  const unsigned long long total = ing_scan_level2<unsigned long long>(blk_tot, (lines + ING_SCAN_BLOCK - 1u) / ING_SCAN_BLOCK);
+  if (threadIdx.x == 0) {
+    const uint32_t heads = (uint32_t)(total >> 32);
+    // FASTA: the last head's record goes on in the next chunk unless this one is the file's last
+    uint32_t n_reads = format == GMX_INGEST_FORMAT_FASTA && !st->final_chunk ? (heads ? heads - 1u : 0u) : heads;
+    if (n_reads > cap_reads) {
+      n_reads = 0;
+      atomicOr(&st->flags, GMX_INGEST_TOO_MANY_LINES);
+    } else {
+      line_base[lines] = (uint32_t)total;  // (the arrays have room for cap_lines + 2 lines and cap_reads + 2 records)
+      rec_line[heads] = lines;
+    }
+    st->n_heads = heads;
+    st->n_reads = n_reads;
+  }
+}
+__global__ void __launch_bounds__(256) gmx_seq_lines3_kernel(const IngestState *st, const uint32_t *line_end, const uint16_t *line_rec, uint32_t *line_base,
+                                                             const unsigned long long *blk_tot, uint32_t *rec_line) {
+  if (st->flags & GMX_INGEST_TOO_MANY_LINES) return;
+  const uint32_t lines = ing_seq_lines(st, line_end);
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < lines; i += gridDim.x * blockDim.x) {
+    const unsigned long long t = blk_tot[i / ING_SCAN_BLOCK];
+    const uint32_t lr = line_rec[i];
+    line_base[i] += (uint32_t)t;
+    if (lr & ING_HEAD) rec_line[(uint32_t)(t >> 32) + (lr & (ING_HEAD - 1u))] = i;  // (at most n_heads - 1 <= cap_reads)
+  }
+}
+__global__ void __launch_bounds__(256) gmx_seq_records_kernel(IngestState *st, const uint32_t *line_end, uint32_t format, const uint32_t *line_base,
+                                                              const uint32_t *rec_line, uint32_t *rec_start, uint32_t *rec_len, uint8_t *skip) {
+  if (st->flags & GMX_INGEST_TOO_MANY_LINES) return;
+  const uint32_t lo = st->text_start, hi = lo + st->text_len, n_nl = st->n_lines, n_reads = st->n_reads, heads = st->n_heads;
+  const bool fasta = format == GMX_INGEST_FORMAT_FASTA;
+  uint32_t mn = 0xFFFFFFFFu, mx = 0;
+  unsigned long long bases = 0;
+  for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n_reads; r += gridDim.x * blockDim.x) {
+    const uint32_t l0 = rec_line[r], l1 = rec_line[r + 1u], b0 = line_base[l0];
+    const uint32_t len = line_base[l1] - b0;
+    const uint32_t j = fasta ? l0 + 1u : l0;  // the first line that may hold bases
+    const bool one_line = len == 0 || line_base[j + 1u] - line_base[j] == len;
+    rec_start[r] = !one_line ? ING_MULTI : len ? ing_seq_line_start(line_end, j, lo) : lo;
+    rec_len[r] = len;
+    skip[r] = 0;
+    mn = min(mn, len);
+    mx = max(mx, len);
+    bases += len;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const uint32_t lines = ing_seq_lines(st, line_end);
+    // FASTA: bases in front of the first head belong to no record (the host reader would take the file for one read per line)
+    if (fasta && (heads ? line_base[rec_line[0]] : line_base[lines]) != 0) atomicOr(&st->flags, GMX_INGEST_BAD_RECORD);
+    uint32_t end = hi;
+    if (!st->final_chunk) end = fasta ? (heads ? ing_seq_line_start(line_end, rec_line[heads - 1u], lo) : lo) : (n_nl ? line_end[n_nl - 1u] + 1u : lo);
+    st->consumed = end;
+    st->tail_len = hi - end;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    mn = min(mn, (uint32_t)__shfl_down(mn, off));
+    mx = max(mx, (uint32_t)__shfl_down(mx, off));
+    bases += __shfl_down(bases, off);
+  }
+  if ((threadIdx.x & 63u) == 0) {
+    if (mn != 0xFFFFFFFFu) atomicMin(&st->min_len, mn);
+    if (mx) atomicMax(&st->max_len, mx);
+    if (bases) atomicAdd(&st->n_bases, bases);
+  }
+}
+// letters src[0, m) -> bits [at, at + m) of a pair of planes (the arithmetic of gmx_fq_pack_kernel)
+__device__ __forceinline__ void ing_pack_letters(const uint8_t *src, uint32_t m, uint32_t at, uint32_t &lo, uint32_t &hi, bool &ok) {
+  for (uint32_t j = 0; j < m; ++j) {
+    const uint32_t c = src[j], u = c & 0xDFu;
+    ok = ok && (u == 0x41u || u == 0x43u || u == 0x47u || u == 0x54u);
+    const uint32_t h = (c >> 2) & 1u;
+    hi |= h << (at + j);
+    lo |= (((c >> 1) & 1u) ^ h) << (at + j);
+  }
+}
+__global__ void __launch_bounds__(256) gmx_seq_pack_kernel(const uint8_t *text, IngestState *st, const uint32_t *line_end, const uint32_t *line_base,
+                                                           const uint32_t *rec_line, const uint32_t *rec_start, const uint32_t *rec_len,
+                                                           const unsigned long long *offsets, unsigned long long *planes, uint8_t *skip) {
+  if (st->flags & (GMX_INGEST_TOO_MANY_LINES | GMX_INGEST_BAD_RECORD)) return;
+  const uint32_t n_reads = st->n_reads, uniform = st->uniform_len, text_lo = st->text_start;
+  const uint32_t wpr = (st->max_len + 31u) / 32u + (uniform ? 0u : 1u);
+  const unsigned long long items = (unsigned long long)n_reads * wpr;
+  for (unsigned long long it = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += (unsigned long long)gridDim.x * blockDim.x) {
+    const uint32_t r = (uint32_t)(it / wpr), w = (uint32_t)(it - (unsigned long long)r * wpr);
+    const uint32_t len = rec_len[r];
+    unsigned long long first, count;
+    if (uniform) {
+      first = (unsigned long long)r * wpr;
+      count = wpr;
+    } else {
+      const unsigned long long off = offsets[r];
+      first = (off >> 5) + r;
+      count = ((off + len) >> 5) - (off >> 5) + 1ull;
+    }
+    if (w >= count) continue;
+    uint32_t lo = 0, hi = 0;
+    bool ok = true;
+    if (w * 32u < len) {
+      const uint32_t m = min(32u, len - w * 32u), start = rec_start[r];
+      if (start != ING_MULTI) {
+        ing_pack_letters(text + start + w * 32u, m, 0u, lo, hi, ok);
+      } else {
+        uint32_t a = rec_line[r], b = rec_line[r + 1u];
+        const uint32_t target = line_base[a] + w * 32u;  // the base wanted, counted over the chunk: in the last line of [a, b) that starts at or in front of it
+        while (b - a > 1u) {
+          const uint32_t mid = a + (b - a) / 2u;
+          if (line_base[mid] <= target) a = mid;
+          else b = mid;
+        }
+        uint32_t at_base = line_base[a], within = target - at_base;
+        for (uint32_t got = 0; got < m; ++a) {  // (bases are left, so lines of the record are: a stays below rec_line[r + 1])
+          const uint32_t next_base = line_base[a + 1u];
+          const uint32_t take = min(m - got, next_base - at_base - within);
+          if (take) ing_pack_letters(text + ing_seq_line_start(line_end, a, text_lo) + within, take, got, lo, hi, ok);
+          got += take;
+          within = 0;
+          at_base = next_base;
+        }
+      }
+    }
+    planes[first + w] = (unsigned long long)lo | ((unsigned long long)hi << 32);
+    if (!ok) {
+      skip[r] = 1;
+      st->any_skip = 1;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // plain gzip (one deflate stream per member, members concatenated): the chunk's compressed bytes cut into PIECES decoded side
 // by side, with the rules of gmx_pargz.h:
 //   gmx_gz_decode_kernel   one wavefront per piece. The first piece of a file starts behind the gzip header, the first of a later
@@ -1719,6 +1926,10 @@ struct gmx_ingest {
     unsigned long long *d_off_blk = nullptr;  // (the scans' block sums: gmx_tile_scan1/2_kernel, gmx_offsets1/2/3_kernel)
     unsigned long long *d_planes = nullptr, *d_offsets = nullptr;
     uint8_t *d_skip = nullptr;
+    // FASTA / LINES (allocated by the first gmx_ingest_set_format that asks for one of them): per line, per record, per 1024 lines
+    uint16_t *d_line_rec = nullptr;
+    uint32_t *d_line_base = nullptr, *d_rec_line = nullptr;
+    unsigned long long *d_line_blk = nullptr;
     IngestState *d_state = nullptr, *h_state = nullptr;
     IngestMember *h_members = nullptr;  // page-locked staging of the member table
     IngestInflateStatus *d_inflate_status = nullptr;
@@ -1732,6 +1943,7 @@ struct gmx_ingest {
     uint32_t deferred_text = 0;  // ... bytes of text of its members
   } slot[GMX_INGEST_SLOTS];
   int last_slot = -1;  // the slot whose chunk the next one continues (-1: a file's first chunk)
+  int format = GMX_INGEST_FORMAT_FASTQ;  // gmx_ingest_set_format
   std::vector<void *> allocs;
   int check_crc = 1;
   uint32_t exp_mode = 0;
@@ -1753,7 +1965,10 @@ int ing_alloc(gmx_ingest *g, T **p, size_t count, bool zero) {
   void *q = nullptr;
   const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
   ING_TRY(hipMalloc(&q, bytes));
-  if (zero) ING_TRY(hipMemset(q, 0, bytes));
+  if (zero) {  // (hipMemset returns before the device is done, and the ingest's streams do not wait for the NULL stream: wait here)
+    ING_TRY(hipMemset(q, 0, bytes));
+    ING_TRY(hipStreamSynchronize(nullptr));
+  }
   g->allocs.push_back(q);
   *p = static_cast<T *>(q);
   return GMX_OK;
@@ -1871,6 +2086,32 @@ uint64_t gmx_ingest_max_text(const gmx_ingest *g) { return g ? g->max_text : 0; 
 uint64_t gmx_ingest_max_compressed(const gmx_ingest *g) { return g ? g->max_comp : 0; }
 uint64_t gmx_ingest_max_members(const gmx_ingest *g) { return g ? g->cap_members : 0; }
 
+int gmx_ingest_set_format(gmx_ingest *g, int format) try {
+  if (!g || (format != GMX_INGEST_FORMAT_FASTQ && format != GMX_INGEST_FORMAT_FASTA && format != GMX_INGEST_FORMAT_LINES)) {
+    gmx_set_error("gmx_ingest_set_format: null ingest or unknown format");
+    return GMX_EINVAL;
+  }
+  for (const auto &s : g->slot)
+    if (s.in_flight || s.deferred) {
+      gmx_set_error("gmx_ingest_set_format: a slot's chunk is in flight (the format is set between files)");
+      return GMX_EINVAL;
+    }
+  if (format != GMX_INGEST_FORMAT_FASTQ && !g->slot[GMX_INGEST_SLOTS - 1].d_line_blk) {  // the line tables, once
+    ING_TRY(hipSetDevice(g->device));
+    g->allocs.reserve(g->allocs.size() + 4 * GMX_INGEST_SLOTS);
+    for (auto &s : g->slot) {
+      int rc;
+      if ((!s.d_line_rec && (rc = ing_alloc(g, &s.d_line_rec, (size_t)g->cap_lines + 2, false))) ||
+          (!s.d_line_base && (rc = ing_alloc(g, &s.d_line_base, (size_t)g->cap_lines + 2, false))) ||
+          (!s.d_rec_line && (rc = ing_alloc(g, &s.d_rec_line, (size_t)g->cap_reads + 2, false))) ||
+          (!s.d_line_blk && (rc = ing_alloc(g, &s.d_line_blk, (size_t)g->cap_lines / ING_SCAN_BLOCK + 2, false))))
+        return rc;
+    }
+  }
+  g->format = format;
+  return GMX_OK;
+} GMX_GUARD_INT("gmx_ingest_set_format")
+
 int gmx_ingest_reset(gmx_ingest *g) try {  // the next chunk starts a file: nothing is carried into it
   if (!g) {
     gmx_set_error("null ingest");
@@ -1934,13 +2175,26 @@ static int ing_enqueue_scan(gmx_ingest *g, int si, uint32_t members_text, int fi
   hipLaunchKernelGGL(gmx_tile_scan1_kernel, dim3(n_tile_blk), dim3(64), 0, g->stream, s.d_tiles, n_tiles, s.d_tile_blk);
   hipLaunchKernelGGL(gmx_tile_scan2_kernel, dim3(1), dim3(64), 0, g->stream, s.d_tile_blk, n_tile_blk, s.d_state, g->cap_lines);
   hipLaunchKernelGGL(gmx_nl_mark_kernel, dim3(n_tiles), dim3(256), 0, g->stream, s.d_text, s.d_state, s.d_tiles, s.d_tile_blk, s.d_line_end, g->cap_lines);
-  hipLaunchKernelGGL(gmx_records_kernel, dim3(2048), dim3(256), 0, g->stream, s.d_text, s.d_state, s.d_line_end, s.d_rec_start, s.d_rec_len, s.d_skip, g->cap_reads);
+  const uint32_t fmt = (uint32_t)g->format;
+  if (fmt == GMX_INGEST_FORMAT_FASTQ) {
+    hipLaunchKernelGGL(gmx_records_kernel, dim3(2048), dim3(256), 0, g->stream, s.d_text, s.d_state, s.d_line_end, s.d_rec_start, s.d_rec_len, s.d_skip, g->cap_reads);
+  } else {  // (the chunk's line count is on the device: blocks beyond it leave at once)
+    const uint32_t n_line_blk = (uint32_t)(((uint64_t)g->cap_lines + 1 + ING_SCAN_BLOCK - 1) / ING_SCAN_BLOCK);
+    hipLaunchKernelGGL(gmx_seq_lines1_kernel, dim3(n_line_blk), dim3(64), 0, g->stream, s.d_text, s.d_state, s.d_line_end, fmt, s.d_line_rec, s.d_line_base, s.d_line_blk);
+    hipLaunchKernelGGL(gmx_seq_lines2_kernel, dim3(1), dim3(64), 0, g->stream, s.d_state, s.d_line_end, fmt, s.d_line_blk, s.d_line_base, s.d_rec_line, g->cap_reads);
+    hipLaunchKernelGGL(gmx_seq_lines3_kernel, dim3(4096), dim3(256), 0, g->stream, s.d_state, s.d_line_end, s.d_line_rec, s.d_line_base, s.d_line_blk, s.d_rec_line);
+    hipLaunchKernelGGL(gmx_seq_records_kernel, dim3(2048), dim3(256), 0, g->stream, s.d_state, s.d_line_end, fmt, s.d_line_base, s.d_rec_line, s.d_rec_start, s.d_rec_len, s.d_skip);
+  }
   const uint32_t n_off_blk = (uint32_t)((g->cap_reads + ING_SCAN_BLOCK - 1) / ING_SCAN_BLOCK);  // (the chunk's read count is on the device: blocks beyond it leave at once)
   hipLaunchKernelGGL(gmx_layout_kernel, dim3(1), dim3(64), 0, g->stream, s.d_state, inflate || gz_len ? s.d_inflate_status : nullptr);
   hipLaunchKernelGGL(gmx_offsets1_kernel, dim3(n_off_blk), dim3(64), 0, g->stream, s.d_state, s.d_rec_len, s.d_offsets, s.d_off_blk);
   hipLaunchKernelGGL(gmx_offsets2_kernel, dim3(1), dim3(64), 0, g->stream, s.d_state, s.d_offsets, s.d_off_blk);
   hipLaunchKernelGGL(gmx_offsets3_kernel, dim3(n_off_blk), dim3(64), 0, g->stream, s.d_state, s.d_offsets, s.d_off_blk);
-  hipLaunchKernelGGL(gmx_fq_pack_kernel, dim3(4096), dim3(256), 0, g->stream, s.d_text, s.d_state, s.d_rec_start, s.d_rec_len, s.d_offsets, s.d_planes, s.d_skip);
+  if (fmt == GMX_INGEST_FORMAT_FASTQ)
+    hipLaunchKernelGGL(gmx_fq_pack_kernel, dim3(4096), dim3(256), 0, g->stream, s.d_text, s.d_state, s.d_rec_start, s.d_rec_len, s.d_offsets, s.d_planes, s.d_skip);
+  else
+    hipLaunchKernelGGL(gmx_seq_pack_kernel, dim3(4096), dim3(256), 0, g->stream, s.d_text, s.d_state, s.d_line_end, s.d_line_base, s.d_rec_line, s.d_rec_start,
+                       s.d_rec_len, s.d_offsets, s.d_planes, s.d_skip);
   ING_TRY(hipGetLastError());
   ING_TRY(hipMemcpyAsync(s.h_state, s.d_state, sizeof(IngestState), hipMemcpyDeviceToHost, g->stream));
   ING_TRY(hipEventRecord(s.done, g->stream));

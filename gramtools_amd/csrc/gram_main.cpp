@@ -916,6 +916,27 @@ static bool bgzf_member_at(const unsigned char *in, size_t size, size_t at, gmx_
   return m->isize <= 65536u;
 }
 
+// What a reads file holds, as the general reader (SeqReader::next) decides it: by the first byte of the first line that is not
+// blank ('@' FASTQ, '>' FASTA, anything else one read per line). Only the head of the file is looked at; zlib inflates it where
+// the file is compressed (BGZF and plain gzip alike). The device chain scans all three (gmx_ingest_set_format); every ingest_*
+// function below sets g_reads_format on the ingests it uses, so the caller sets it once per file.
+static int g_reads_format = GMX_INGEST_FORMAT_FASTQ;
+static int detect_reads_format(const std::string &path) {
+  gzFile gz = gzopen(path.c_str(), "rb");
+  if (!gz) return GMX_INGEST_FORMAT_FASTQ;
+  char buf[1 << 14];
+  const int got = gzread(gz, buf, sizeof(buf));
+  gzclose(gz);
+  for (int i = 0; i < got; ++i) {
+    if (buf[i] == '\n' || (buf[i] == '\r' && i + 1 < got && buf[i + 1] == '\n')) continue;  // blank lines, "\r\n" too
+    return buf[i] == '@' ? GMX_INGEST_FORMAT_FASTQ : buf[i] == '>' ? GMX_INGEST_FORMAT_FASTA : GMX_INGEST_FORMAT_LINES;
+  }
+  return GMX_INGEST_FORMAT_FASTQ;  // (nothing but blank lines in 16 KB: the host reader's)
+}
+static const char *reads_format_scanner() {
+  return g_reads_format == GMX_INGEST_FORMAT_FASTA ? "FASTA scanner" : g_reads_format == GMX_INGEST_FORMAT_LINES ? "one-read-per-line scanner" : "FASTQ scanner";
+}
+
 struct DeviceFeed {  // one per process: the ingest object and its page-locked staging, sized by the largest file seen
   gmx_ingest *ing = nullptr;
   uint64_t max_text = 0;
@@ -987,6 +1008,7 @@ int ingest_bgzf_file(const std::string &path, int threads, int device, OnChunk o
   if (!df.ing) return 1;
   gmx_ingest *ing = df.ing;
   GMX_CHECK(gmx_ingest_reset(ing));
+  GMX_CHECK(gmx_ingest_set_format(ing, g_reads_format));
   // (a chunk holds at most what the ingest's member table holds: a file of many tiny members must not be refused by the submit)
   const uint64_t kMembers = std::min<uint64_t>(device_feed_members(), gmx_ingest_max_members(ing));
   const uint64_t max_text = gmx_ingest_max_text(ing), max_comp = gmx_ingest_max_compressed(ing);
@@ -1087,6 +1109,7 @@ int ingest_bgzf_file(const std::string &path, int threads, int device, OnChunk o
       const bool decoder = (res.status & (GMX_INGEST_BAD_MEMBER | GMX_INGEST_BAD_CRC | GMX_INGEST_TOO_MANY_LINES)) != 0;
       if (!decoder) {  // the text itself is not four-line FASTQ: the host's fast path would say the same
         if (*delivered == 0) return 1;
+        if (g_reads_format != GMX_INGEST_FORMAT_FASTQ) return 2;  // (FASTA / one read per line: the general reader takes over)
         die("gram: " + path + ": irregular FASTQ record after the first " + std::to_string(*delivered) +
             " reads (multi-line or blank lines); decompress and reformat, or use a four-line FASTQ");
       }
@@ -1143,6 +1166,7 @@ int ingest_bgzf_file_dealt(const std::string &path, int threads, const std::vect
     device_feed_prepare(devs[k], device_feed_text_for(file_text), 0, &feed(k));
     if (!feed(k).ing) return 1;
     GMX_CHECK(gmx_ingest_reset(feed(k).ing));
+    GMX_CHECK(gmx_ingest_set_format(feed(k).ing, g_reads_format));
   }
   feed_trace("ingests of all engines ready");
   const uint64_t max_text = gmx_ingest_max_text(feed(0).ing), max_comp = gmx_ingest_max_compressed(feed(0).ing);
@@ -1202,6 +1226,7 @@ int ingest_bgzf_file_dealt(const std::string &path, int threads, const std::vect
       const bool decoder = (res.status & (GMX_INGEST_BAD_MEMBER | GMX_INGEST_BAD_CRC | GMX_INGEST_TOO_MANY_LINES)) != 0;
       if (!decoder) {
         if (*delivered == 0) return 1;
+        if (g_reads_format != GMX_INGEST_FORMAT_FASTQ) return 2;
         die("gram: " + path + ": irregular FASTQ record after the first " + std::to_string(*delivered) +
             " reads (multi-line or blank lines); decompress and reformat, or use a four-line FASTQ");
       }
@@ -1233,6 +1258,9 @@ int ingest_bgzf_file_dealt(const std::string &path, int threads, const std::vect
 // front-end: 2.8 x), the host parser from 32 threads on. GMX_DEVICE_FASTQ=1 / GMX_HOST_FASTQ=1 force either.
 static bool plain_fastq_on_device(int max_threads, size_t n_engines) {
   if (getenv("GMX_HOST_FASTQ")) return false;
+  // FASTA / one read per line: no parallel host parser exists for them (parse_fastq_file declines), the alternative is the
+  // general reader on ONE thread: the device route at every thread count
+  if (g_reads_format != GMX_INGEST_FORMAT_FASTQ) return true;
   if (const char *e = getenv("GMX_DEVICE_FASTQ")) return atoi(e) != 0;
   (void)n_engines;  // (several engines: the same rule — the chunks are then dealt over the engines' ingests, ingest_text_file_dealt; measured
                     //  only with several engines on ONE GPU, tools/feed_x8.py, where it has nothing to gain)
@@ -1252,7 +1280,9 @@ static bool looks_like_plain_fastq(const std::string &path, uint64_t *size_out) 
   if (fd < 0) return false;
   struct stat sb;
   unsigned char h[2] = {0, 0};
-  const bool ok = fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size >= 4 && pread(fd, h, 2, 0) == 2 && h[0] == '@';
+  // (FASTA / one read per line, as detect_reads_format found: any first byte — blank lines may lead — but gzip's)
+  const bool ok = fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size >= 4 && pread(fd, h, 2, 0) == 2 &&
+                  (g_reads_format == GMX_INGEST_FORMAT_FASTQ ? h[0] == '@' : !(h[0] == 0x1f && h[1] == 0x8b));
   close(fd);
   if (ok && size_out) *size_out = (uint64_t)sb.st_size;
   return ok;
@@ -1285,6 +1315,7 @@ static int text_chunk_verdict(const gmx_ingest_result &res, const std::string &p
   if (!res.status) return 0;
   if (res.status & GMX_INGEST_BAD_RECORD) {  // not four-line FASTQ: the host's fast path would say the same
     if (delivered == 0) return 1;
+    if (g_reads_format != GMX_INGEST_FORMAT_FASTQ) return 2;  // (FASTA / one read per line: the general reader takes over and skips what was mapped)
     die("gram: " + path + ": irregular FASTQ record after the first " + std::to_string(delivered) +
         " reads (multi-line or blank lines); reformat, or use a four-line FASTQ");
   }
@@ -1304,6 +1335,7 @@ int ingest_text_file(const std::string &path, int threads, int device, OnChunk o
   if (!df.ing) return 1;
   gmx_ingest *ing = df.ing;
   GMX_CHECK(gmx_ingest_reset(ing));
+  GMX_CHECK(gmx_ingest_set_format(ing, g_reads_format));
   const unsigned T = (unsigned)std::max(1, std::min(threads, 64));
   const size_t n_chunks = (size_t)((size + chunk - 1) / chunk);
   auto bytes_of = [&](size_t ci) { return (size_t)std::min<uint64_t>(chunk, size - (uint64_t)ci * chunk); };
@@ -1435,6 +1467,7 @@ int ingest_gzip_file(const std::string &path, int threads, int device, OnChunk o
   if (!df.ing || gmx_ingest_max_compressed(df.ing) < chunk + look) return 1;
   gmx_ingest *ing = df.ing;
   GMX_CHECK(gmx_ingest_reset(ing));
+  GMX_CHECK(gmx_ingest_set_format(ing, g_reads_format));
   const unsigned T = (unsigned)std::max(1, std::min(threads, 64));
   const size_t n_chunks = (size_t)((size + chunk - 1) / chunk);
   auto fail_chunk = [&]() -> size_t {
@@ -1502,6 +1535,7 @@ int ingest_text_file_dealt(const std::string &path, int threads, const std::vect
     device_feed_prepare(devs[k], std::max<uint64_t>(chunk, 1u << 16) + (1u << 16), 0, &feed(k));
     if (!feed(k).ing) return 1;
     GMX_CHECK(gmx_ingest_reset(feed(k).ing));
+    GMX_CHECK(gmx_ingest_set_format(feed(k).ing, g_reads_format));
   }
   const size_t n_chunks = (size_t)((size + chunk - 1) / chunk);
   const unsigned T = (unsigned)std::max(1, std::min(threads, 64));
@@ -1690,6 +1724,8 @@ int run_parse_check(const std::string &path, int threads) {
       GMX_CHECK(gmx_ingest_fetch_reads(g_device_feed.ing, slot, blk.planes.data(), blk.offsets.data(), blk.skip.data()));
       collect(blk);
     };
+    // ("any": the format detected and set as `gram genotype` does; else four-line FASTQ only, as before the other scanners existed)
+    g_reads_format = std::string(getenv("GMX_PARSE_CHECK_DEVICE")) == "any" ? detect_reads_format(path) : GMX_INGEST_FORMAT_FASTQ;
     int rc = ingest_bgzf_file(path, threads, 0, take, &delivered);
     if (rc == 1 && delivered == 0) rc = ingest_gzip_file(path, threads, 0, take, &delivered);  // (plain gzip: pieces decoded side by side)
     if (rc == 1 && delivered == 0) rc = ingest_text_file(path, threads, 0, take, &delivered);  // (not BGZF: plain text through the same kernels)
@@ -1952,7 +1988,9 @@ int run_genotype(const Args &a) {
         if (bg && hipSetDeviceForPrewarm(devices[0])) {
           const uint64_t text = device_feed_text_for((uint64_t)sb.st_size * 6);
           device_feed_prepare(devices[0], text, std::min<uint64_t>((uint64_t)sb.st_size, text / 2) + 64);
-        } else if (h[0] == '@' && plain_fastq_on_device(max_threads, devices.size()) && fstat_ok_size(smp.reads[0]) >= 4) {  // plain FASTQ: text chunks (ingest_text_file)
+        } else if (!(h[0] == 0x1f && h[1] == 0x8b) && fstat_ok_size(smp.reads[0]) >= 4) {  // plain FASTQ / FASTA / one read per line: text chunks (ingest_text_file)
+          g_reads_format = detect_reads_format(smp.reads[0]);  // (the files' loop sets it again; nothing reads it in between)
+          if ((g_reads_format == GMX_INGEST_FORMAT_FASTQ && h[0] != '@') || !plain_fastq_on_device(max_threads, devices.size())) break;
           const uint64_t chunk = std::min<uint64_t>(device_feed_text_chunk(1), fstat_ok_size(smp.reads[0]));  // (a nested PRG's larger chunks: sized when the file is opened)
           device_feed_prepare(devices[0], std::max<uint64_t>(chunk, 1u << 16) + (1u << 16), chunk + 64);
         }
@@ -2069,7 +2107,9 @@ int run_genotype(const Args &a) {
     // start and drops the reads already mapped. With several engines the file's chunks are dealt round: every GPU decodes and maps
     // its share (ingest_bgzf_file_dealt), the record a chunk's end cuts travels to the next GPU through the host.
     uint64_t skip_reads = 0;
+    g_reads_format = GMX_INGEST_FORMAT_FASTQ;
     if (!getenv("GMX_HOST_GZ")) {
+      g_reads_format = detect_reads_format(path);  // FASTA and one read per line take the same device routes (gmx_ingest_set_format)
       static std::vector<std::unique_ptr<HostBuf<uint32_t>>> dev_seeds;  // per engine and slot
       while (dev_seeds.size() < 3 * devices.size()) dev_seeds.emplace_back(new HostBuf<uint32_t>());
       uint64_t delivered = 0;
@@ -2128,7 +2168,7 @@ int run_genotype(const Args &a) {
       }
       if (rc == 2) {
         sync_all();
-        std::cerr << "warning: " << path << ": the device-side " << (text_route ? "FASTQ scanner" : gz_route ? "gzip decoder" : "BGZF decoder") << " gave up after " << delivered << " reads; the host reader takes over" << std::endl;
+        std::cerr << "warning: " << path << ": the device-side " << (text_route ? reads_format_scanner() : gz_route ? "gzip decoder" : "BGZF decoder") << " gave up after " << delivered << " reads; the host reader takes over" << std::endl;
         skip_reads = delivered;
         in_file = 0;               // (the host reader counts the file's reads from its start again)
         total_reads -= delivered;
@@ -2161,7 +2201,8 @@ int run_genotype(const Args &a) {
       seed_stream.base = file_base + (in_file + kBatch - 1) / kBatch * kBatch;
       continue;
     }
-    if (skip_reads) die("gram: " + path + ": the device-side decoder delivered reads of a file the host readers cannot parse");
+    // (FASTA / one read per line: the general reader below is the one that takes over, and skips what was mapped)
+    if (skip_reads && g_reads_format == GMX_INGEST_FORMAT_FASTQ) die("gram: " + path + ": the device-side decoder delivered reads of a file the host readers cannot parse");
     // (the general reader below draws from `master`: bring it to where the stream stands)
     master.seed(seed);
     master.discard(seed_stream.base);
@@ -2185,6 +2226,12 @@ int run_genotype(const Args &a) {
     while (reader.next(rec)) {
       if (in_batch == 0)
         for (auto &s : batch_seeds) s = (uint32_t)master();  // always 5000 draws per batch
+      if (skip_reads) {  // a read the device feed already mapped: it keeps its place in the batches, nothing else
+        --skip_reads;
+        if (++in_batch == kBatch) in_batch = 0;
+        total_reads++;
+        continue;
+      }
       encode_read(rec.seq, bases);  // an unencodable read stays as an empty read: counted as skipped, keeps its seed
       offsets.push_back(bases.size());
       seeds.push_back(batch_seeds[in_batch]);

@@ -20,6 +20,7 @@ from ._lib import check
 
 RNG_LEMIRE = 0
 GMX_INGEST_BAD_RECORD, GMX_INGEST_BAD_MEMBER, GMX_INGEST_BAD_CRC, GMX_INGEST_TOO_MANY_LINES = 1, 2, 4, 8  # gmx_ingest_result.status
+GMX_INGEST_FORMAT_FASTQ, GMX_INGEST_FORMAT_FASTA, GMX_INGEST_FORMAT_LINES = 0, 1, 2  # gmx_ingest_set_format
 RNG_DIVISION = 1
 GROUPED_LOG = 0xFFFFFFFF
 
@@ -694,8 +695,8 @@ def bgzf_members(data) -> list:
 
 
 class Ingest:
-    """Reads files decoded on the device (include/gmx.h, gmx_ingest_*): BGZF members inflated, four-line records found and
-    packed into bit planes by HIP kernels; three slots (0, 1, 2) taken in turn. ``submit_bgzf`` / ``submit_text`` / ``submit_gzip`` enqueue a chunk, ``wait`` returns
+    """Reads files decoded on the device (include/gmx.h, gmx_ingest_*): BGZF members inflated, records (four-line FASTQ; FASTA or one read per
+    line after ``set_format``) found and packed into bit planes by HIP kernels; three slots (0, 1, 2) taken in turn. ``submit_bgzf`` / ``submit_text`` / ``submit_gzip`` enqueue a chunk, ``wait`` returns
     its gmx_ingest_result; Quasimapper.map_ingested maps what a slot holds."""
 
     def __init__(self, device: int = 0, max_text_bytes: int = 64 << 20):
@@ -713,6 +714,10 @@ class Ingest:
 
     def reset(self):
         check(self.lib.gmx_ingest_reset(self.h))
+
+    def set_format(self, fmt: int):
+        """What the chunks submitted from here on hold (between files): GMX_INGEST_FORMAT_FASTQ (the default), _FASTA or _LINES."""
+        check(self.lib.gmx_ingest_set_format(self.h, fmt))
 
     @staticmethod
     def member_array(members):

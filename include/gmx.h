@@ -218,7 +218,8 @@ void *gmx_engine_second_stream(gmx_engine *e);
  * Replaces the reference's reads reader for gzipped FASTQ — SeqRead over zlib / htslib on one host thread
  * (include/sequence_read/seqread.hpp:94-180, quasimap.cpp:65-76) — for BGZF files (bgzip, htslib, BCL Convert: gzip members
  * of <= 64 KB that carry their size in a `BC` extra field, SAM spec §4.1): the compressed members are uploaded as they lie in
- * the file and HIP kernels inflate them (one wavefront per member, CRC-32 checked), find the four-line records and pack
+ * the file and HIP kernels inflate them (one wavefront per member, CRC-32 checked), find the records — four-line FASTQ, or
+ * FASTA / one read per line after gmx_ingest_set_format — and pack
  * their bases into the bit planes of gmx_map_reads_packed_host, all in HBM. A file is handed over in CHUNKS of whole
  * members, in order; a record cut by a chunk's end is carried into the next chunk on the device. THREE slots (0, 1, 2) take
  * the chunks in turn, so that two chunks upload and inflate — their inflate kernels side by side: a kernel's last wavefronts
@@ -237,7 +238,9 @@ typedef struct {
   uint32_t crc32;    /* of that text (the trailer) */
   uint32_t reserved;
 } gmx_bgzf_member;
-#define GMX_INGEST_BAD_RECORD 1u      /* not plain four-line FASTQ (blank / multi-line record, '@' or '+' missing, lengths differ) */
+#define GMX_INGEST_BAD_RECORD 1u      /* the text is not what the ingest's format says. FASTQ: not plain four-line records (blank / multi-line
+                                       * record, '@' or '+' missing, lengths differ). FASTA: sequence in front of the first '>' line. LINES: a
+                                       * line that starts with '@' or '>'. Every format: a record of more than 1 MB cut by a chunk's end */
 #define GMX_INGEST_BAD_MEMBER 2u      /* a member's deflate data could not be decoded */
 #define GMX_INGEST_BAD_CRC 4u         /* a member's text does not match its trailer */
 #define GMX_INGEST_TOO_MANY_LINES 8u  /* more lines / records than the ingest has room for (lines of a few bytes) */
@@ -266,6 +269,21 @@ uint64_t gmx_ingest_max_text(const gmx_ingest *g);
 uint64_t gmx_ingest_max_compressed(const gmx_ingest *g);
 uint64_t gmx_ingest_max_members(const gmx_ingest *g); /* most members a chunk may hold (files of many tiny members) */
 int gmx_ingest_reset(gmx_ingest *g); /* the next chunk is a file's first: nothing is carried into it */
+/* What the text holds, for every chunk submitted afterwards through any of the submit calls below, until set again. Called between
+ * files (next to gmx_ingest_reset); GMX_EINVAL for another value or while a slot's chunk is in flight. An ingest on which it is
+ * never called reads four-line FASTQ. The rules are those of `gram`'s general host reader:
+ *   FASTA  a record starts at a line whose first byte is '>'; its read is every line up to the next such line (or the file's
+ *          end) put together, each without its '\n' and ONE '\r' in front of it. Blank lines add nothing, also in front of the
+ *          first '>'. A '>' line directly followed by another, or by the file's end, is a read of length 0 and counts. A chunk's
+ *          records end at its last '>' line (the read there may go on): that line and what follows are carried.
+ *   LINES  every non-empty line (after the same stripping) is a read; blank lines do not count.
+ * Results as for FASTQ: planes, uniform_len or d_offsets, d_skip for reads with a byte other than ACGTacgt. A chunk whose reads
+ * all have length 0 comes with uniform_len == 0 and d_offsets (n_pairs == n_reads). The first call that asks for FASTA or LINES
+ * allocates the line tables (3 bytes per 4 bytes of max_text_bytes and slot); nothing is allocated while a file is read. */
+#define GMX_INGEST_FORMAT_FASTQ 0 /* four-line FASTQ: the default */
+#define GMX_INGEST_FORMAT_FASTA 1
+#define GMX_INGEST_FORMAT_LINES 2
+int gmx_ingest_set_format(gmx_ingest *g, int format);
 /* `compressed` (host memory; page-locked = asynchronous upload) must stay untouched until the slot's gmx_ingest_wait. */
 int gmx_ingest_submit_bgzf(gmx_ingest *g, int slot, const uint8_t *compressed, uint64_t n_bytes, const gmx_bgzf_member *members,
                            uint64_t n_members, int final_chunk);
