@@ -31,7 +31,7 @@ from .quasimap import (  # noqa: F401
     dump_grouped_allele_counts,
     RNG_LEMIRE,
     GMX_INGEST_BAD_RECORD, GMX_INGEST_BAD_MEMBER, GMX_INGEST_BAD_CRC, GMX_INGEST_TOO_MANY_LINES,
-    GMX_INGEST_FORMAT_FASTQ, GMX_INGEST_FORMAT_FASTA, GMX_INGEST_FORMAT_LINES,
+    GMX_INGEST_FORMAT_FASTQ, GMX_INGEST_FORMAT_FASTA, GMX_INGEST_FORMAT_LINES, GMX_INGEST_FORMAT_BAM,
     RNG_DIVISION,
 )
 from ._lib import GmxError  # noqa: F401

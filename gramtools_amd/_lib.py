@@ -118,6 +118,8 @@ SYMBOLS = {
     "gmx_ingest_max_compressed": (_u64, [_vp]),
     "gmx_ingest_reset": (C.c_int, [_vp]),
     "gmx_ingest_set_format": (C.c_int, [_vp, C.c_int]),
+    "gmx_ingest_set_bam_header": (C.c_int, [_vp, _u64]),
+    "gmx_ingest_bam_rewalks": (_i64, [_vp]),
     "gmx_ingest_submit_bgzf": (C.c_int, [_vp, C.c_int, _vp, _u64, C.POINTER(BgzfMember), _u64, C.c_int]),
     "gmx_ingest_submit_text": (C.c_int, [_vp, C.c_int, _vp, _u64, C.c_int]),
     "gmx_ingest_submit_gzip": (C.c_int, [_vp, C.c_int, _vp, _u64, _u64, C.c_int]),

@@ -19,6 +19,7 @@
 #include <zlib.h>
 
 #include <atomic>
+#include <cctype>
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -103,17 +104,42 @@ std::string join(const std::string &dir, const std::string &name) {
   return dir.back() == '/' ? dir + name : dir + "/" + name;
 }
 
-// ---- sequence file reader: FASTQ / FASTA / one-sequence-per-line, optionally gzipped -------------------
-// (the reference uses the third-party seq_file reader, include/sequence_read/seq_file.h; SAM/BAM/CRAM need
-// htslib and are not supported here)
+// ---- sequence file reader: FASTQ / FASTA / one-sequence-per-line, optionally gzipped; BAM -------------------
+// (the reference uses the third-party seq_file reader, include/sequence_read/seq_file.h, which reads SAM / BAM / CRAM through
+// htslib. BAM is read here — the layout and the rules are in include/gmx.h, GMX_INGEST_FORMAT_BAM —; SAM and CRAM are refused.)
 struct SeqRecord {
   std::string seq, qual;
 };
+// A reads file is BAM when its (inflated) head starts with "BAM\1", whatever its name. Names that promise what the content does
+// not hold, or a format that is not read, end the run: until BAM was read, all of these were taken for one read per line.
+static bool has_suffix_nocase(const std::string &path, const char *suffix) {
+  const size_t n = strlen(suffix);
+  if (path.size() < n) return false;
+  for (size_t i = 0; i < n; ++i)
+    if (std::tolower((unsigned char)path[path.size() - n + i]) != suffix[i]) return false;
+  return true;
+}
+static bool reads_head_is_bam(const std::string &path, const char *head, int got) {
+  const bool bam = got >= 4 && memcmp(head, "BAM\1", 4) == 0;
+  if (bam) return true;
+  if (has_suffix_nocase(path, ".sam") || has_suffix_nocase(path, ".cram"))
+    die("gram: " + path + ": SAM and CRAM reads files are not supported; convert with `samtools view -b` (to BAM) or `samtools fastq`");
+  if (has_suffix_nocase(path, ".bam")) die("gram: " + path + ": named .bam, but its content is not BAM (no \"BAM\\1\" behind the BGZF layer)");
+  return false;
+}
 class SeqReader {
  public:
-  explicit SeqReader(const std::string &path) : gz_(gzopen(path.c_str(), "rb")) {
+  explicit SeqReader(const std::string &path) : path_(path), gz_(gzopen(path.c_str(), "rb")) {
     if (!gz_) die("Cannot open reads file: " + path);
     gzbuffer(gz_, 1 << 20);
+    char head[4];
+    const int got = gzread(gz_, head, 4);
+    bam_ = reads_head_is_bam(path, head, got);
+    if (bam_) {
+      bam_header();
+      return;
+    }
+    if (gzrewind(gz_) != 0) die("gram: " + path + ": cannot rewind the reads file");
     have_line_ = next_line(line_);
   }
   ~SeqReader() {
@@ -122,6 +148,7 @@ class SeqReader {
   bool next(SeqRecord &r) {
     r.seq.clear();
     r.qual.clear();
+    if (bam_) return bam_next(r);
     while (have_line_ && line_.empty()) have_line_ = next_line(line_);
     if (!have_line_) return false;
     if (line_[0] == '@') {  // FASTQ (multi-line tolerant)
@@ -167,9 +194,96 @@ class SeqReader {
     }
     return any;
   }
+  // ---- BAM: gzread delivers the concatenated members' text -------------------------------------------------------
+  [[noreturn]] void bam_die(const std::string &what) { die("gram: " + path_ + ": " + what); }
+  size_t bam_read(void *dst, size_t n) {  // up to n bytes; fewer: the text's end
+    size_t have = 0;
+    while (have < n) {
+      const int got = gzread(gz_, static_cast<char *>(dst) + have, (unsigned)std::min<size_t>(n - have, 1u << 30));
+      if (got < 0) {
+        int err = 0;
+        const char *msg = gzerror(gz_, &err);
+        bam_die(std::string("error reading the reads file: ") + (msg ? msg : "zlib error"));
+      }
+      if (got == 0) break;
+      have += (size_t)got;
+    }
+    return have;
+  }
+  static int32_t le32(const unsigned char *p) { return (int32_t)((uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24); }
+  int32_t bam_i32(const char *what) {
+    unsigned char b[4];
+    if (bam_read(b, 4) != 4) bam_die(std::string("truncated BAM header (") + what + ")");
+    return le32(b);
+  }
+  void bam_skip(uint64_t n, const char *what) {
+    char buf[1 << 12];
+    while (n) {
+      const size_t want = (size_t)std::min<uint64_t>(n, sizeof(buf));
+      if (bam_read(buf, want) != want) bam_die(std::string("truncated BAM header (") + what + ")");
+      n -= want;
+    }
+  }
+  void bam_header() {  // behind the magic: l_text, text, n_ref, n_ref times { l_name, name, l_ref }
+    const int32_t l_text = bam_i32("l_text");
+    if (l_text < 0) bam_die("malformed BAM header (l_text < 0)");
+    bam_skip((uint64_t)l_text, "text");
+    const int32_t n_ref = bam_i32("n_ref");
+    if (n_ref < 0) bam_die("malformed BAM header (n_ref < 0)");
+    header_bytes_ = 12ull + (uint64_t)l_text;
+    for (int32_t i = 0; i < n_ref; ++i) {
+      const int32_t l_name = bam_i32("reference name length");
+      if (l_name < 0) bam_die("malformed BAM header (reference name length < 0)");
+      bam_skip((uint64_t)l_name + 4, "reference");
+      header_bytes_ += 8ull + (uint64_t)l_name;
+    }
+  }
+  bool bam_next(SeqRecord &r) {
+    unsigned char b[4];
+    const size_t got = bam_read(b, 4);
+    if (got == 0) return false;
+    const std::string which = "BAM record " + std::to_string(bam_index_);
+    if (got != 4) bam_die(which + " is truncated (the file ends inside its block_size)");
+    const int32_t bs = le32(b);
+    if (bs < 32) bam_die(which + " is malformed (block_size " + std::to_string(bs) + ")");
+    rec_.resize(32);  // (a wild block_size must not become a wild allocation: the fixed fields first)
+    if (bam_read(rec_.data(), 32) != 32) bam_die(which + " is truncated (the file ends inside it)");
+    const unsigned char *f = rec_.data();
+    const uint32_t l_name = f[8], n_cigar = (uint32_t)f[12] | (uint32_t)f[13] << 8, flag = (uint32_t)f[14] | (uint32_t)f[15] << 8;
+    const int32_t l_seq = le32(f + 16);
+    if (l_name == 0 || l_seq < 0 || (uint64_t)bs < 32ull + l_name + 4ull * n_cigar + ((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq)
+      bam_die(which + " is malformed (block_size " + std::to_string(bs) + ", l_read_name " + std::to_string(l_name) + ", n_cigar_op " + std::to_string(n_cigar) +
+              ", l_seq " + std::to_string(l_seq) + ")");
+    rec_.resize((size_t)bs);
+    f = rec_.data();
+    if (bam_read(rec_.data() + 32, (size_t)bs - 32) != (size_t)bs - 32) bam_die(which + " is truncated (the file ends inside it)");
+    const unsigned char *seq = rec_.data() + 32 + l_name + 4 * (size_t)n_cigar, *qual = seq + ((size_t)l_seq + 1) / 2;
+    const bool reverse = (flag & 0x10u) != 0;
+    static const char fwd[] = "=ACMGRSVTWYHKDBN", rev[] = "=TGKCYWBASRDMHVN";  // (the reference's seq_comp_table: a code's four bits in reverse order, but S <-> W)
+    r.seq.resize((size_t)l_seq);
+    r.qual.resize((size_t)l_seq);
+    for (size_t i = 0; i < (size_t)l_seq; ++i) {
+      const size_t j = reverse ? (size_t)l_seq - 1 - i : i;
+      const unsigned code = (j & 1) ? seq[j >> 1] & 15u : seq[j >> 1] >> 4;
+      r.seq[i] = reverse ? rev[code] : fwd[code];
+      r.qual[i] = (char)(unsigned char)(33u + qual[j]);  // (absent qualities, 0xFF: byte 32, which counts as -1 a base — as in the reference)
+    }
+    ++bam_index_;
+    return true;
+  }
+
+ public:
+  bool is_bam() const { return bam_; }
+  uint64_t bam_header_bytes() const { return header_bytes_; }  // the header's length in the file's text, magic included
+
+ private:
+  std::string path_;
   gzFile gz_;
   std::string line_;
   bool have_line_ = false;
+  bool bam_ = false;
+  uint64_t header_bytes_ = 0, bam_index_ = 0;
+  std::vector<unsigned char> rec_;
 };
 
 // encode_dna_bases (common/utils.cpp:73-92): A,C,G,T -> 1..4; anything else => the whole read is dropped
@@ -917,7 +1031,7 @@ static bool bgzf_member_at(const unsigned char *in, size_t size, size_t at, gmx_
 }
 
 // What a reads file holds, as the general reader (SeqReader::next) decides it: by the first byte of the first line that is not
-// blank ('@' FASTQ, '>' FASTA, anything else one read per line). Only the head of the file is looked at; zlib inflates it where
+// blank ('@' FASTQ, '>' FASTA, anything else one read per line); BAM by its magic. Only the head of the file is looked at; zlib inflates it where
 // the file is compressed (BGZF and plain gzip alike). The device chain scans all three (gmx_ingest_set_format); every ingest_*
 // function below sets g_reads_format on the ingests it uses, so the caller sets it once per file.
 static int g_reads_format = GMX_INGEST_FORMAT_FASTQ;
@@ -927,6 +1041,7 @@ static int detect_reads_format(const std::string &path) {
   char buf[1 << 14];
   const int got = gzread(gz, buf, sizeof(buf));
   gzclose(gz);
+  if (reads_head_is_bam(path, buf, got)) return GMX_INGEST_FORMAT_BAM;  // (ends the run for a .sam, a .cram, and a .bam that is none)
   for (int i = 0; i < got; ++i) {
     if (buf[i] == '\n' || (buf[i] == '\r' && i + 1 < got && buf[i + 1] == '\n')) continue;  // blank lines, "\r\n" too
     return buf[i] == '@' ? GMX_INGEST_FORMAT_FASTQ : buf[i] == '>' ? GMX_INGEST_FORMAT_FASTA : GMX_INGEST_FORMAT_LINES;
@@ -934,7 +1049,7 @@ static int detect_reads_format(const std::string &path) {
   return GMX_INGEST_FORMAT_FASTQ;  // (nothing but blank lines in 16 KB: the host reader's)
 }
 static const char *reads_format_scanner() {
-  return g_reads_format == GMX_INGEST_FORMAT_FASTA ? "FASTA scanner" : g_reads_format == GMX_INGEST_FORMAT_LINES ? "one-read-per-line scanner" : "FASTQ scanner";
+  return g_reads_format == GMX_INGEST_FORMAT_BAM ? "BAM record chain" : g_reads_format == GMX_INGEST_FORMAT_FASTA ? "FASTA scanner" : g_reads_format == GMX_INGEST_FORMAT_LINES ? "one-read-per-line scanner" : "FASTQ scanner";
 }
 
 struct DeviceFeed {  // one per process: the ingest object and its page-locked staging, sized by the largest file seen
@@ -1009,6 +1124,12 @@ int ingest_bgzf_file(const std::string &path, int threads, int device, OnChunk o
   gmx_ingest *ing = df.ing;
   GMX_CHECK(gmx_ingest_reset(ing));
   GMX_CHECK(gmx_ingest_set_format(ing, g_reads_format));
+  const bool bam = g_reads_format == GMX_INGEST_FORMAT_BAM;
+  if (bam) {  // the header's length in the file's text: zlib inflates the file's head (a header that cannot be read: the host reader says why)
+    SeqReader head(path);
+    if (!head.is_bam()) return 1;
+    GMX_CHECK(gmx_ingest_set_bam_header(ing, head.bam_header_bytes()));
+  }
   // (a chunk holds at most what the ingest's member table holds: a file of many tiny members must not be refused by the submit)
   const uint64_t kMembers = std::min<uint64_t>(device_feed_members(), gmx_ingest_max_members(ing));
   const uint64_t max_text = gmx_ingest_max_text(ing), max_comp = gmx_ingest_max_compressed(ing);
@@ -1098,7 +1219,7 @@ int ingest_bgzf_file(const std::string &path, int threads, int device, OnChunk o
     if (n_staged > n_submitted) submit();
     gmx_ingest_result res;
     GMX_CHECK(gmx_ingest_wait(ing, (int)(ci % 3), &res));
-    feed_trace("chunk decoded");
+    feed_trace(bam ? "BAM chunk chained and packed" : "chunk decoded");
     if (const char *tf = getenv("GMX_INGEST_TEST_FAIL_CHUNK"))  // test hook: the device decoder "gives up" on this chunk (tests/test_ingest.py)
       if ((size_t)atoll(tf) == ci) res.status |= GMX_INGEST_BAD_MEMBER;
     if (res.status) {
@@ -1106,6 +1227,7 @@ int ingest_bgzf_file(const std::string &path, int threads, int device, OnChunk o
         gmx_ingest_result drop;
         GMX_CHECK(gmx_ingest_wait(ing, (int)(cj % 3), &drop));
       }
+      if (bam) return 2;  // whatever the status: the host reader takes the file over, and names a malformed record
       const bool decoder = (res.status & (GMX_INGEST_BAD_MEMBER | GMX_INGEST_BAD_CRC | GMX_INGEST_TOO_MANY_LINES)) != 0;
       if (!decoder) {  // the text itself is not four-line FASTQ: the host's fast path would say the same
         if (*delivered == 0) return 1;
@@ -1119,7 +1241,7 @@ int ingest_bgzf_file(const std::string &path, int threads, int device, OnChunk o
     on_chunk(res, (int)(ci % 3));
     *delivered += res.n_reads;
   }
-  if (bad_walk) return *delivered == 0 ? 1 : 2;  // bytes that are no BGZF member behind the chunks delivered: the host reader's
+  if (bad_walk) return *delivered == 0 && !bam ? 1 : 2;  // bytes that are no BGZF member behind the chunks delivered: the host reader's
   return 0;
 }
 
@@ -1698,7 +1820,8 @@ int run_parse_check(const std::string &path, int threads) {
       fast.offsets.push_back(fast.bases.size());
     }
   };
-  if (parse_fastq_file(path, threads, collect))
+  const bool is_bam = detect_reads_format(path) == GMX_INGEST_FORMAT_BAM;  // (the fast path would inflate a block of it to find no '@')
+  if (!is_bam && parse_fastq_file(path, threads, collect))
     std::cout << "fast " << fast.offsets.size() - 1 << " " << fast.bases.size() << " " << fnv(fast) << std::endl;
   else
     std::cout << "fast declined" << std::endl;
@@ -1726,9 +1849,10 @@ int run_parse_check(const std::string &path, int threads) {
     };
     // ("any": the format detected and set as `gram genotype` does; else four-line FASTQ only, as before the other scanners existed)
     g_reads_format = std::string(getenv("GMX_PARSE_CHECK_DEVICE")) == "any" ? detect_reads_format(path) : GMX_INGEST_FORMAT_FASTQ;
+    const bool dev_bam = g_reads_format == GMX_INGEST_FORMAT_BAM;  // (BAM: BGZF or nothing)
     int rc = ingest_bgzf_file(path, threads, 0, take, &delivered);
-    if (rc == 1 && delivered == 0) rc = ingest_gzip_file(path, threads, 0, take, &delivered);  // (plain gzip: pieces decoded side by side)
-    if (rc == 1 && delivered == 0) rc = ingest_text_file(path, threads, 0, take, &delivered);  // (not BGZF: plain text through the same kernels)
+    if (rc == 1 && delivered == 0 && !dev_bam) rc = ingest_gzip_file(path, threads, 0, take, &delivered);  // (plain gzip: pieces decoded side by side)
+    if (rc == 1 && delivered == 0 && !dev_bam) rc = ingest_text_file(path, threads, 0, take, &delivered);  // (not BGZF: plain text through the same kernels)
     if (rc == 0)
       std::cout << "device " << fast.offsets.size() - 1 << " " << fast.bases.size() << " " << fnv(fast) << std::endl;
     else
@@ -2108,8 +2232,12 @@ int run_genotype(const Args &a) {
     // its share (ingest_bgzf_file_dealt), the record a chunk's end cuts travels to the next GPU through the host.
     uint64_t skip_reads = 0;
     g_reads_format = GMX_INGEST_FORMAT_FASTQ;
-    if (!getenv("GMX_HOST_GZ")) {
-      g_reads_format = detect_reads_format(path);  // FASTA and one read per line take the same device routes (gmx_ingest_set_format)
+    // (every file's format is looked at, whatever the route: a .sam, a .cram or a .bam that is none ends the run here)
+    const int path_format = detect_reads_format(path);
+    const bool is_bam = path_format == GMX_INGEST_FORMAT_BAM;
+    // BAM: the device route at every --max_threads with one engine; several engines: the host reader into the group feed
+    if (!getenv("GMX_HOST_GZ") && !(is_bam && devices.size() > 1)) {
+      g_reads_format = path_format;  // FASTA, one read per line and BAM take the same device routes (gmx_ingest_set_format)
       static std::vector<std::unique_ptr<HostBuf<uint32_t>>> dev_seeds;  // per engine and slot
       while (dev_seeds.size() < 3 * devices.size()) dev_seeds.emplace_back(new HostBuf<uint32_t>());
       uint64_t delivered = 0;
@@ -2151,10 +2279,10 @@ int run_genotype(const Args &a) {
                      : ingest_bgzf_file(path, max_threads, devices[0], [&](const gmx_ingest_result &res, int slot) { map_chunk(res, 0, slot); }, &delivered);
       // plain gzip, one engine: decoded on the device too, at any --max_threads (the host's inflation is the
       // slower at every thread count); several engines keep the host reader (the stream's window would travel through the host)
-      const bool gz_route = rc == 1 && delivered == 0 && devices.size() == 1 && looks_like_gzip(path, nullptr);
+      const bool gz_route = rc == 1 && delivered == 0 && !is_bam && devices.size() == 1 && looks_like_gzip(path, nullptr);
       if (gz_route) rc = ingest_gzip_file(path, max_threads, devices[0], [&](const gmx_ingest_result &res, int slot) { map_chunk(res, 0, slot); }, &delivered);
       // not BGZF: plain four-line FASTQ takes the same route minus the inflate kernel (round 6; GMX_HOST_FASTQ=1: the host parser)
-      const bool text_route = rc == 1 && delivered == 0 && !gz_route && plain_fastq_on_device(max_threads, devices.size());
+      const bool text_route = rc == 1 && delivered == 0 && !is_bam && !gz_route && plain_fastq_on_device(max_threads, devices.size());
       if (text_route)
         rc = dealt ? ingest_text_file_dealt(path, max_threads, devices, map_chunk, &delivered)
                    : ingest_text_file(path, max_threads, devices[0], [&](const gmx_ingest_result &res, int slot) { map_chunk(res, 0, slot); }, &delivered);
@@ -2168,7 +2296,7 @@ int run_genotype(const Args &a) {
       }
       if (rc == 2) {
         sync_all();
-        std::cerr << "warning: " << path << ": the device-side " << (text_route ? reads_format_scanner() : gz_route ? "gzip decoder" : "BGZF decoder") << " gave up after " << delivered << " reads; the host reader takes over" << std::endl;
+        std::cerr << "warning: " << path << ": the device-side " << (text_route || is_bam ? reads_format_scanner() : gz_route ? "gzip decoder" : "BGZF decoder") << " gave up after " << delivered << " reads; the host reader takes over" << std::endl;
         skip_reads = delivered;
         in_file = 0;               // (the host reader counts the file's reads from its start again)
         total_reads -= delivered;
@@ -2197,7 +2325,7 @@ int run_genotype(const Args &a) {
       }
       total_reads += n;
     };
-    if (parse_fastq_file(path, max_threads, sink)) {
+    if (!is_bam && parse_fastq_file(path, max_threads, sink)) {
       seed_stream.base = file_base + (in_file + kBatch - 1) / kBatch * kBatch;
       continue;
     }

@@ -20,7 +20,7 @@ from ._lib import check
 
 RNG_LEMIRE = 0
 GMX_INGEST_BAD_RECORD, GMX_INGEST_BAD_MEMBER, GMX_INGEST_BAD_CRC, GMX_INGEST_TOO_MANY_LINES = 1, 2, 4, 8  # gmx_ingest_result.status
-GMX_INGEST_FORMAT_FASTQ, GMX_INGEST_FORMAT_FASTA, GMX_INGEST_FORMAT_LINES = 0, 1, 2  # gmx_ingest_set_format
+GMX_INGEST_FORMAT_FASTQ, GMX_INGEST_FORMAT_FASTA, GMX_INGEST_FORMAT_LINES, GMX_INGEST_FORMAT_BAM = 0, 1, 2, 3  # gmx_ingest_set_format
 RNG_DIVISION = 1
 GROUPED_LOG = 0xFFFFFFFF
 
@@ -695,8 +695,8 @@ def bgzf_members(data) -> list:
 
 
 class Ingest:
-    """Reads files decoded on the device (include/gmx.h, gmx_ingest_*): BGZF members inflated, records (four-line FASTQ; FASTA or one read per
-    line after ``set_format``) found and packed into bit planes by HIP kernels; three slots (0, 1, 2) taken in turn. ``submit_bgzf`` / ``submit_text`` / ``submit_gzip`` enqueue a chunk, ``wait`` returns
+    """Reads files decoded on the device (include/gmx.h, gmx_ingest_*): BGZF members inflated, records (four-line FASTQ; FASTA, one read per
+    line or BAM after ``set_format``, BAM with ``set_bam_header`` after every ``reset``) found and packed into bit planes by HIP kernels; three slots (0, 1, 2) taken in turn. ``submit_bgzf`` / ``submit_text`` / ``submit_gzip`` enqueue a chunk, ``wait`` returns
     its gmx_ingest_result; Quasimapper.map_ingested maps what a slot holds."""
 
     def __init__(self, device: int = 0, max_text_bytes: int = 64 << 20):
@@ -716,8 +716,20 @@ class Ingest:
         check(self.lib.gmx_ingest_reset(self.h))
 
     def set_format(self, fmt: int):
-        """What the chunks submitted from here on hold (between files): GMX_INGEST_FORMAT_FASTQ (the default), _FASTA or _LINES."""
+        """What the chunks submitted from here on hold (between files): GMX_INGEST_FORMAT_FASTQ (the default), _FASTA, _LINES or _BAM."""
         check(self.lib.gmx_ingest_set_format(self.h, fmt))
+
+    def set_bam_header(self, header_bytes: int):
+        """GMX_INGEST_FORMAT_BAM, after ``reset`` in front of a file's first chunk: the first header_bytes bytes of the file's text
+        are its header (magic, text, reference table) and are skipped, however many chunks they span."""
+        check(self.lib.gmx_ingest_set_bam_header(self.h, header_bytes))
+
+    def bam_rewalks(self) -> int:
+        """Test hook: tiles of BAM chunks whose guess was wrong and whose second walk, from the true entry, added records (since the ingest was created)."""
+        n = self.lib.gmx_ingest_bam_rewalks(self.h)
+        if n < 0:
+            check(int(n))
+        return int(n)
 
     @staticmethod
     def member_array(members):

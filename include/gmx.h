@@ -240,10 +240,11 @@ typedef struct {
 } gmx_bgzf_member;
 #define GMX_INGEST_BAD_RECORD 1u      /* the text is not what the ingest's format says. FASTQ: not plain four-line records (blank / multi-line
                                        * record, '@' or '+' missing, lengths differ). FASTA: sequence in front of the first '>' line. LINES: a
-                                       * line that starts with '@' or '>'. Every format: a record of more than 1 MB cut by a chunk's end */
+                                       * line that starts with '@' or '>'. BAM: a malformed record (below), or the file's text ends inside its
+                                       * header. Every format: a record of more than 1 MB cut by a chunk's end */
 #define GMX_INGEST_BAD_MEMBER 2u      /* a member's deflate data could not be decoded */
 #define GMX_INGEST_BAD_CRC 4u         /* a member's text does not match its trailer */
-#define GMX_INGEST_TOO_MANY_LINES 8u  /* more lines / records than the ingest has room for (lines of a few bytes) */
+#define GMX_INGEST_TOO_MANY_LINES 8u  /* more lines / records than the ingest has room for (lines of a few bytes; BAM: records without bases) */
 /* plain gzip only (gmx_ingest_submit_gzip): */
 #define GMX_INGEST_GZ_UNREPAIRED 16u   /* a piece whose speculative start did not line up could not be decoded from its predecessor's end */
 #define GMX_INGEST_GZ_LOOKAHEAD 32u    /* the chunk's last block does not end inside the look-ahead bytes given */
@@ -283,7 +284,33 @@ int gmx_ingest_reset(gmx_ingest *g); /* the next chunk is a file's first: nothin
 #define GMX_INGEST_FORMAT_FASTQ 0 /* four-line FASTQ: the default */
 #define GMX_INGEST_FORMAT_FASTA 1
 #define GMX_INGEST_FORMAT_LINES 2
+#define GMX_INGEST_FORMAT_BAM 3
 int gmx_ingest_set_format(gmx_ingest *g, int format);
+/* BAM (GMX_INGEST_FORMAT_BAM): the text — a BGZF file's inflated bytes through gmx_ingest_submit_bgzf, or those bytes themselves
+ * through gmx_ingest_submit_text, cut anywhere — is a header and then records, all integers little-endian:
+ *   header  "BAM\1", l_text:i32, text[l_text], n_ref:i32, n_ref times { l_name:i32, name[l_name], l_ref:i32 }
+ *   record  block_size:i32, then block_size bytes: refID:i32 pos:i32 l_read_name:u8 mapq:u8 bin:u16 n_cigar_op:u16 flag:u16
+ *           l_seq:i32 next_refID:i32 next_pos:i32 tlen:i32 (32 bytes), read_name[l_read_name], cigar[4 * n_cigar_op],
+ *           seq[(l_seq + 1) / 2], qual[l_seq], tags. Base i of seq is the high nibble of byte i / 2 when i is even, the low one
+ *           when odd; the codes index "=ACMGRSVTWYHKDBN" (A, C, G, T = 1, 2, 4, 8).
+ * The rules (the reference's seq_read over htslib, which is not seq_read_primary): EVERY record is a read, in file order —
+ * unmapped, secondary and supplementary ones too; the read is the l_seq bases, reversed and complemented (A<->T, C<->G) when
+ * flag & 0x10; a code other than 1, 2, 4, 8 ('=' and N included) sets the read's skip flag; l_seq == 0 is a read of length 0
+ * and counts. A record is MALFORMED when block_size < 32 + l_read_name + 4 * n_cigar_op + (l_seq + 1) / 2 + l_seq, when
+ * l_read_name == 0, when l_seq < 0, or when the text ends inside it in the file's last chunk. The reference takes a malformed
+ * record for the end of the file, silently; here it is an error: GMX_INGEST_BAD_RECORD (`gram`: its host reader takes the file
+ * over and exits 1 with the record's index). A missing BGZF EOF marker is accepted.
+ * gmx_ingest_set_bam_header, after gmx_ingest_reset (and _set_format) in front of a file's first chunk: the first header_bytes
+ * bytes of the file's text are its header — the caller finds the length by inflating the file's head — and are skipped, however
+ * many chunks they span. GMX_EINVAL in another format or with a chunk in flight.
+ * Records are found by a chain pass: tiles of GMX_BAM_TILE bytes (default 4 KB) walked side by side from
+ * speculative starts, linked in order, and walked again where the speculation was wrong — a record is only ever accepted when
+ * block_size links lead to it from the file's first record, whatever its tags look like. A chunk's records end at its last
+ * complete record; the rest is carried. gmx_ingest_submit_gzip, the _deferred submits and gmx_ingest_scan return GMX_EINVAL in
+ * this format. The first gmx_ingest_set_format(BAM) allocates the tile tables (about an eighth of max_text_bytes per slot);
+ * nothing is allocated while a file is read. */
+int gmx_ingest_set_bam_header(gmx_ingest *g, uint64_t header_bytes);
+int64_t gmx_ingest_bam_rewalks(gmx_ingest *g); /* test hook: tiles whose guess was wrong and whose second walk, from the true entry, added records; since creation */
 /* `compressed` (host memory; page-locked = asynchronous upload) must stay untouched until the slot's gmx_ingest_wait. */
 int gmx_ingest_submit_bgzf(gmx_ingest *g, int slot, const uint8_t *compressed, uint64_t n_bytes, const gmx_bgzf_member *members,
                            uint64_t n_members, int final_chunk);
