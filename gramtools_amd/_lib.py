@@ -34,7 +34,7 @@ class Stats(C.Structure):
 class QueueCounts(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("mapped", "alive", "dead", "overflow_probe", "overflow_extend", "big_mapped",
                                           "cover_general", "cover_mid", "cover_overflow", "seed_cursor", "huge_search",
-                                          "inst_mapped", "huge_cover", "log_replays", "log_replayed_entries")]
+                                          "inst_mapped", "huge_cover", "log_replays", "log_replayed_entries", "overflow_split")]
 
 
 class StockReport(C.Structure):
@@ -158,6 +158,9 @@ SYMBOLS = {
     "gmx_coverage_reduce_end": (C.c_int, [_vp, _vp]),
     "gmx_coverage_fetch": (C.c_int, [_vp, _u32p, _u32p, _u32p, C.POINTER(Stats)]),
     "gmx_coverage_fetch_grouped_log": (_i64, [_vp, _u32p, _u64]),
+    "gmx_engine_record_outcomes": (C.c_int, [_vp, C.c_int]),
+    "gmx_engine_outcome_count": (_i64, [_vp]),
+    "gmx_engine_fetch_outcomes": (C.c_int, [_vp, _u64, _u64, _u8p]),
     "gmx_coverage_import_grouped_log": (C.c_int, [_vp, _u32p, _u64, C.c_int]),
     "gmx_grouped_log_merge_gathered": (_i64, [_vp, _vp, C.c_int, _u64, _vp, _u64]),
     "gmx_finalize_u16": (None, [_u32p, _u64, C.c_int]),
@@ -185,6 +188,8 @@ SYMBOLS = {
     "gmx_group_map_reads_packed_host": (C.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _u64]),
     "gmx_group_sync_uploads": (C.c_int, [_vp]),
     "gmx_group_allreduce": (C.c_int, [_vp]),
+    "gmx_group_outcome_count": (_i64, [_vp]),
+    "gmx_group_fetch_outcomes": (C.c_int, [_vp, _u64, _u64, _u8p]),
     "gmx_comm_unique_id": (C.c_int, [_u8p]),
     "gmx_comm_create": (C.c_int, [_u8p, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),
     "gmx_comm_destroy": (None, [_vp]),

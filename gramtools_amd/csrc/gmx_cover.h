@@ -1168,7 +1168,8 @@ GMX_HD bool gmx_final_items(const GmxIndexView &ix, const GmxFinalState *finals,
 // ---------------------------------------------------------------------------
 template <class Env>
 GMX_HD void gmx_cover_task(const GmxIndexView &ix, Env &env, const GmxFinalState *finals, uint32_t n_final,
-                           uint32_t read_len, uint32_t seed, int rng_mode) {
+                           uint32_t read_len, uint32_t seed, int rng_mode, uint32_t *drawn_from = nullptr) {
+  // drawn_from (optional): how many mapping instances the selection drew from (0: it did not draw)
   typedef GmxScratch<Env> S;
   if (n_final == 1 && (finals[0].lo == finals[0].hi || gmx_text_form(finals[0].hi))) {
     if (!ix.is_nested) {
@@ -1250,6 +1251,7 @@ GMX_HD void gmx_cover_task(const GmxIndexView &ix, Env &env, const GmxFinalState
     env.fail(GMX_TASK_ERROR);
     return;
   }
+  if (drawn_from) *drawn_from = total;
   GMX_COVER_PROF(env, 2);
   if (r <= nonvariant) return;
   const uint32_t want = r - nonvariant - 1;  // 0-based index in the ordered map

@@ -279,7 +279,9 @@ __device__ uint32_t gmx_tail_item(const GmxIndexView &ix, const BatchView &b, co
     nf = ctx.n_out;
     if (nf == 0) {
       // its read counter
-      atomicAdd(&acc.stats[all_kmers_present(ix.kmer_bitmap, ix.kmer_size, r) ? 3 : 2], 1ull);
+      const bool present = all_kmers_present(ix.kmer_bitmap, ix.kmer_size, r);
+      atomicAdd(&acc.stats[present ? 3 : 2], 1ull);
+      if (o.outcomes) gmx_outcome_put(o, task, present ? GMX_OUTCOME_NO_EXTENSION : GMX_OUTCOME_MISSING_KMER);
       o.n_final[task] = 0;
       return GMX_TASK_MAPPED;
     }
@@ -318,12 +320,15 @@ __device__ uint32_t gmx_tail_item(const GmxIndexView &ix, const BatchView &b, co
   env.log_sites = acc.log_sites;
   env.status = GMX_TASK_MAPPED;
   env.log_at = 0;
-  gmx_cover_task(ix, env, finals, nf, len, b.seeds[task >> 1], acc.rng_mode);
+  uint32_t drawn_from = 0;
+  gmx_cover_task(ix, env, finals, nf, len, b.seeds[task >> 1], acc.rng_mode, &drawn_from);
   env.log_abandon();
   if (env.status == GMX_TASK_MAPPED && is_search) {
     atomicAdd(&acc.stats[4], 1ull);  // exact_mapped
+    if (o.outcomes) gmx_outcome_put(o, task, GMX_OUTCOME_MAPPED);
     o.n_final[task] = nf;
   }
+  if (o.outcomes && env.status == GMX_TASK_MAPPED && drawn_from > 1u) gmx_outcome_multi(o, task);
   return env.status;
 }
 
@@ -445,8 +450,10 @@ __global__ void __launch_bounds__(GMX_BLOCK) gmx_cover_kernel(GmxIndexView ix, B
     env.prof(6);  // from the start of the kernel (first task of the lane) or the end of the lane's previous task
     atomicAdd(&gmx_cover_stats[LIST * 16 + 7], 1ull);
 #endif
-    gmx_cover_task(ix, env, finals, nf, len, b.seeds[read], acc.rng_mode);
+    uint32_t drawn_from = 0;
+    gmx_cover_task(ix, env, finals, nf, len, b.seeds[read], acc.rng_mode, &drawn_from);
     env.log_abandon();
+    if (o.outcomes && env.status == GMX_TASK_MAPPED && drawn_from > 1u) gmx_outcome_multi(o, task);
 #ifdef GMX_LOOP_STATS
     env.prof(5);
     t_kernel = env.prof_t;
@@ -714,8 +721,10 @@ __global__ void __launch_bounds__(64) gmx_cover_coop_kernel(GmxIndexView ix, Bat
     const uint32_t n_classes = __popc(leaders16), rank = __popc(lt & leaders16);
     // --- the draw ---
     bool member = false;
+    uint32_t drawn_from = 0;  // (the same in all lanes of the group)
     if (have && !rejected && !failed && items16 != 0u) {
       uint32_t r = 0;
+      drawn_from = nonvariant + n_classes;
       if (!gmx_uniform_1_to_n(b.seeds[ts.task >> 1], nonvariant + n_classes, acc.rng_mode, r)) {
         err = GMX_TASK_ERROR;
       } else if (r > nonvariant) {
@@ -783,6 +792,7 @@ __global__ void __launch_bounds__(64) gmx_cover_coop_kernel(GmxIndexView ix, Bat
     if (have && gl == 0 && logfull)
       o.log_retry_list[atomicAdd(&o.counters[GMX_CNT_LOG_RETRY * GMX_CNT_STRIDE], 1u)] = entry;
     if (have && gl == 0 && rejected) reject[atomicAdd(reject_n, 1u)] = entry;
+    if (o.outcomes && have && gl == 0 && !rejected && !logfull && drawn_from > 1u) gmx_outcome_multi(o, ts.task);
     if (err != 0u && atomicCAS(&o.error[0], 0u, err) == 0u) o.error[1] = ts.task;
     __syncthreads();  // the scratch is reused by the next round
     GMX_COOP_PHASE(3);

@@ -112,7 +112,15 @@ struct gmx_engine {
   // configs[3] + 11 %, configs[1] +- 0 — so the twin exists for nested PRGs and indexes of 2 GB and more (GMX_TWIN=0 / 1 forces),
   // never for an index whose sites use the grouped log (its replay is per batch).
   gmx_engine *twin = nullptr;
+  gmx_engine *owner = nullptr;  // (of a twin: the engine it belongs to)
   bool is_twin = false, twin_off = false;
+  // Per-read outcomes (gmx_engine_record_outcomes; SearchOut::outcomes): one byte per read handed over since the last reset, in the
+  // ENGINE's buffer whichever workspace runs the launch — a launch is given its first read's index when it is enqueued. Bytes
+  // from outcome_count on are zero (the kernels OR into zeroed words); not an entry of `allocs`: a growing buffer replaces it.
+  bool record_outcomes = false;
+  uint32_t *d_outcomes = nullptr;
+  uint64_t outcome_cap = 0, outcome_count = 0;  // bytes (a multiple of 4) | reads recorded
+  uint64_t outcome_epoch = 0;                   // resets so far (gmx_group: is its ledger of ranges still about this buffer?)
   hipStream_t main_stream = nullptr;  // the twin's main chain (the engine's own: the NULL stream, or the caller's)
   uint32_t twin_toggle = 0;
   hipEvent_t ev_zeroed = nullptr, ev_twin_done = nullptr;  // a queued reset has executed | the twin's last batch has ended
@@ -348,7 +356,37 @@ void gmx_engine_default_opts(gmx_engine_opts *o) try {
   o->log_cap_words = 0;
 } GMX_GUARD_VOID("gmx_engine_default_opts")
 
-static int ensure_batch_capacity(gmx_engine *e, uint64_t n_reads) {
+// room for n_more reads' outcome bytes in the engine's buffer (never while one of its kernels is being enqueued: before the
+// batch's first). Growth waits for the launches in flight — they write the old buffer — and carries their bytes over.
+static int ensure_outcome_capacity(gmx_engine *own, uint64_t n_more) {
+  const uint64_t need = own->outcome_count + n_more;
+  if (need <= own->outcome_cap) return GMX_OK;
+  const uint64_t cap = (std::max<uint64_t>(need + need / 2, 1u << 20) + 3) & ~3ull;
+  uint32_t *q = nullptr;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMalloc((void **)&q, cap));
+  hipError_t err = hipMemset(q, 0, cap);
+  if (err == hipSuccess && own->outcome_count)
+    err = hipMemcpy(q, own->d_outcomes, (own->outcome_count + 3) & ~3ull, hipMemcpyDeviceToDevice);
+  if (err != hipSuccess) {
+    (void)hipFree(q);
+    HIP_TRY(err);
+  }
+  if (own->d_outcomes) (void)hipFree(own->d_outcomes);
+  own->d_outcomes = q;
+  own->outcome_cap = cap;
+  return GMX_OK;
+}
+
+// launching: called for a launch of n_reads reads that is about to be enqueued (the reserve calls size the workspace only)
+static int ensure_batch_capacity(gmx_engine *e, uint64_t n_reads, bool launching = false) {
+  if (launching) {
+    gmx_engine *own = e->owner ? e->owner : e;
+    if (own->record_outcomes) {
+      const int orc = ensure_outcome_capacity(own, n_reads);
+      if (orc) return orc;
+    }
+  }
   if (n_reads <= e->cap_reads) return GMX_OK;
   // (re)allocate: old buffers stay in `allocs` until destroy; growth is rare (first call sizes it)
   // (an eighth of headroom when the workspace GROWS: chunks of a decoded reads file differ by a few reads — the record a chunk's end
@@ -440,6 +478,8 @@ int gmx_engine_create(const gmx_index *ixh, const gmx_engine_opts *opts_in, gmx_
   int rc = engine_create(ixh, opts_in, nullptr, out);
   if (rc) return rc;
   gmx_engine *e = *out;
+  // MEASUREMENT HOOK ONLY (profiles/read_outcomes: the cost of recording in an unchanged benchmark): nothing reads the bytes back
+  if (const char *ro = getenv("GMX_RECORD_OUTCOMES")) e->record_outcomes = atoi(ro) != 0;
   // the twin (a second batch in flight; gmx_engine::twin): nested PRGs and indexes of 2 GB and more
   const gmx::HostIndex &h = gmx_index_host(ixh);
   const bool can = !e->log_sites && e->shared_index && !getenv("GMX_NO_INDEX_SHARE");  // (the twin reads the engine's copy of the index, never one of its own)
@@ -449,6 +489,7 @@ int gmx_engine_create(const gmx_index *ixh, const gmx_engine_opts *opts_in, gmx_
     gmx_engine *t = nullptr;
     if (engine_create(ixh, &e->opts, e, &t) == GMX_OK) {
       e->twin = t;
+      t->owner = e;
     } else {
       (void)hipGetLastError();  // (no room for a second workspace: one batch at a time, as before)
     }
@@ -780,6 +821,7 @@ void gmx_engine_destroy(gmx_engine *e) try {
     if (sl.h_seeds) (void)hipHostFree(sl.h_seeds);
   }
   for (void *p : e->allocs) (void)hipFree(p);
+  if (e->d_outcomes) (void)hipFree(e->d_outcomes);
   gmx_dev_index_release(e->shared_index);
   delete e;
 } GMX_GUARD_VOID("gmx_engine_destroy")
@@ -796,6 +838,9 @@ int gmx_engine_reset(gmx_engine *e) try {
     HIP_TRY(hipMemset(e->twin->d_counters, 0, GMX_N_COUNTERS * GMX_CNT_STRIDE * 4));
     e->twin_in_flight = false;
   }
+  if (e->outcome_count) HIP_TRY(hipMemset(e->d_outcomes, 0, (e->outcome_count + 3) & ~3ull));
+  e->outcome_count = 0;
+  ++e->outcome_epoch;
   e->log_counts.clear();
   e->log_known = e->log_reads_since = 0;
   e->log_state_pending = false;
@@ -809,6 +854,11 @@ int gmx_engine_reset_async(gmx_engine *e, void *hip_stream) try {
   if (frc) return frc;
   if ((frc = twin_join(e, st))) return frc;  // (the zeroing comes behind whatever the twin still records)
   e->twin_in_flight = false;
+  // (the outcome bytes: zeroed on the reset's stream now — behind the batches before, ahead of the next one, whose twin launch waits
+  //  for the accumulators' zeroing, queued on this stream later; the count restarts with the next launch)
+  if (e->outcome_count) HIP_TRY(hipMemsetAsync(e->d_outcomes, 0, (e->outcome_count + 3) & ~3ull, st));
+  e->outcome_count = 0;
+  ++e->outcome_epoch;
   e->reset_pending = true;
   e->reset_stream = st;
   e->log_counts.clear();  // what earlier batches left in the device log goes with the cursor
@@ -980,7 +1030,7 @@ static int launch_batch(gmx_engine *e, const BatchInput &in, hipStream_t stream)
   // retry lists, which a growing workspace (ensure_batch_capacity) replaces with fresh, uninitialised buffers.
   int rc = e->log_sites ? log_settle(e) : GMX_OK;
   if (rc) return rc;
-  if ((rc = ensure_batch_capacity(e, n_reads))) return rc;
+  if ((rc = ensure_batch_capacity(e, n_reads, true))) return rc;
   const bool fold_reset = e->reset_pending && e->reset_stream == stream;
   if (e->reset_pending && !fold_reset && (rc = flush_reset(e))) return rc;
   e->reset_pending = false;
@@ -1049,6 +1099,14 @@ static int launch_batch(gmx_engine *e, const BatchInput &in, hipStream_t stream)
   o.log_retry_recs = e->d_log_retry_recs[e->log_retry_side];
   o.log_retry_huge = e->d_log_retry_huge[e->log_retry_side];
   o.stats = e->d_stats;
+  {
+    gmx_engine *own = e->owner ? e->owner : e;
+    if (own->record_outcomes) {  // (room was made in ensure_batch_capacity)
+      o.outcomes = own->d_outcomes;
+      o.outcome_base = own->outcome_count;
+      own->outcome_count += n_reads;
+    }
+  }
   uint32_t n_tasks = (uint32_t)n_reads * 2;
   if (e->keep_states) {  // test hook: a task that never reaches a kernel that writes its state count reads as "no state"
     HIP_TRY(hipMemsetAsync(e->d_n_final, 0, (size_t)n_tasks * sizeof(uint32_t), stream));
@@ -1938,6 +1996,7 @@ int gmx_engine_queue_counts(gmx_engine *e, gmx_queue_counts *out) try {
   out->huge_cover = c(15);
   out->log_replays = e->log_replays;
   out->log_replayed_entries = e->log_replayed_entries;
+  out->overflow_split = c(29);
   return GMX_OK;
 } GMX_GUARD_INT("gmx_engine_queue_counts")
 
@@ -2032,6 +2091,44 @@ int gmx_coverage_fetch(gmx_engine *e, uint32_t *allele_sum, uint32_t *per_base, 
   return GMX_OK;
 } GMX_GUARD_INT("gmx_coverage_fetch")
 
+int gmx_engine_record_outcomes(gmx_engine *e, int on) try {
+  if (!e) {
+    gmx_set_error("null engine");
+    return GMX_EINVAL;
+  }
+  e->record_outcomes = on != 0;
+  return GMX_OK;
+} GMX_GUARD_INT("gmx_engine_record_outcomes")
+
+int64_t gmx_engine_outcome_count(gmx_engine *e) try {
+  if (!e) {
+    gmx_set_error("null engine");
+    return GMX_EINVAL;
+  }
+  return (int64_t)e->outcome_count;
+} GMX_GUARD_INT("gmx_engine_outcome_count")
+
+int gmx_engine_fetch_outcomes(gmx_engine *e, uint64_t first, uint64_t n, uint8_t *out) try {
+  if (!e || (n && !out)) {
+    gmx_set_error("gmx_engine_fetch_outcomes: null argument");
+    return GMX_EINVAL;
+  }
+  if (first > e->outcome_count || n > e->outcome_count - first) {
+    gmx_set_error("gmx_engine_fetch_outcomes: reads " + std::to_string(first) + " .. " + std::to_string(first + n) + " of " +
+                  std::to_string(e->outcome_count) + " recorded");
+    return GMX_EINVAL;
+  }
+  {
+    int frc = flush_reset(e);
+    if (frc) return frc;
+    if ((frc = log_settle(e))) return frc;  // (a task redone after a full log sets its bits then)
+  }
+  HIP_TRY(hipSetDevice(e->opts.device));
+  HIP_TRY(hipDeviceSynchronize());  // both workspaces' streams
+  if (n) HIP_TRY(hipMemcpy(out, reinterpret_cast<const uint8_t *>(e->d_outcomes) + first, n, hipMemcpyDeviceToHost));
+  return GMX_OK;
+} GMX_GUARD_INT("gmx_engine_fetch_outcomes")
+
 int64_t gmx_coverage_fetch_grouped_log(gmx_engine *e, uint32_t *out, uint64_t cap_words) try {
   if (!e) return GMX_EINVAL;
   if (hipSetDevice(e->opts.device) != hipSuccess) return GMX_EHIP;
@@ -2066,6 +2163,8 @@ int gmx_coverage_import_grouped_log(gmx_engine *e, const uint32_t *records, uint
 } GMX_GUARD_INT("gmx_coverage_import_grouped_log")
 
 }  // extern "C"
+
+uint64_t gmx_engine_outcome_epoch(const gmx_engine *e) { return e->outcome_epoch; }
 
 void gmx_engine_raw(gmx_engine *e, GmxEngineRaw *out) {
   (void)flush_reset(e);

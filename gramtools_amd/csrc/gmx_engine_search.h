@@ -1026,7 +1026,28 @@ struct SearchOut {
 #endif
                              // [0] all (pack kernel) [1] skipped (seed / probe kernel) [2] missing_kmer [3] no_extension
                              // (filter kernels, large-capacity passes) [4] exact_mapped (whoever finished the search)
+  // Per-read outcomes (gmx_engine_record_outcomes; null: not recorded — one uniform branch per site below). One byte per read,
+  // four to a word, read outcome_base + r of the engine's buffer for read r of this launch: bits 0-1 the forward task's code,
+  // 2-3 the reverse-complement task's (GMX_OUTCOME_*), 4 / 5 "its selection drew among several mapping instances". The words
+  // start zeroed and every task ORs its code in exactly once, AT THE PLACE THAT COUNTS IT INTO stats[2..4] (a skipped task's
+  // code is 0: nothing to write) — so a task redone in a larger tier leaves one code, like one count.
+  uint32_t *outcomes;
+  unsigned long long outcome_base;
 };
+// (the task codes: GMX_OUTCOME_* of include/gmx.h)
+#define GMX_OUTCOME_MULTI 16u  // (the forward task's bit; << 1: the reverse-complement task's)
+// The two tasks of a read share a byte and neighbouring reads a word; their kernels run on different streams, and a word may
+// straddle two launches in flight on the two workspaces: a device-scope atomic OR on the word (no return value: fire and forget).
+__device__ __forceinline__ void gmx_outcome_or(const SearchOut &o, uint32_t task, uint32_t bits) {
+  const unsigned long long r = o.outcome_base + (task >> 1);
+  atomicOr(o.outcomes + (r >> 2), bits << (8u * (uint32_t)(r & 3ull)));
+}
+__device__ __forceinline__ void gmx_outcome_put(const SearchOut &o, uint32_t task, uint32_t code) {
+  gmx_outcome_or(o, task, (uint32_t)code << (2u * (task & 1u)));
+}
+__device__ __forceinline__ void gmx_outcome_multi(const SearchOut &o, uint32_t task) {
+  gmx_outcome_or(o, task, GMX_OUTCOME_MULTI << (task & 1u));
+}
 
 #ifndef GMX_REGIONS
 #define GMX_REGIONS 8
@@ -1145,6 +1166,7 @@ __device__ __forceinline__ void finish_lane(const GmxIndexView &ix, const Search
   const uint32_t region = min(__umulhi(ctx.first_pos, o.region_inv), (uint32_t)(GMX_REGIONS - 1));
   enum : uint32_t { Q_OVER = GMX_REGIONS, Q_ALIVE, Q_DEAD, Q_GENERAL, Q_N, Q_SKIPPED = Q_N, Q_COLS };  // Q_SKIPPED: a count only
   const uint32_t cat = mapped ? (compact ? region : Q_GENERAL) : over ? Q_OVER : alive ? Q_ALIVE : dead ? Q_DEAD : 0xFFu;
+  if (o.outcomes && mapped) gmx_outcome_put(o, task, GMX_OUTCOME_MAPPED);  // (counted into stats[4] below)
   __shared__ uint32_t q_cnt[GMX_BLOCK / 64][Q_COLS];
   __shared__ uint32_t q_base[Q_N];
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1566,10 +1588,13 @@ __device__ void gmx_inst_rounds(const GmxIndexView &ix, const BatchView &b, cons
     const uint32_t total = atomicAdd(&o.slot_n_final[slot], 0u);
     if (total > 0) {
       atomicAdd(&o.stats[4], 1ull);
+      if (o.outcomes) gmx_outcome_put(o, task, GMX_OUTCOME_MAPPED);
       o.inst_mapped_list[atomicAdd(&o.counters[25 * GMX_CNT_STRIDE], 1u)] = GMX_ENTRY_INST | slot;
     } else {
       ReadRef rr = task_read(b, task);
-      atomicAdd(&o.stats[all_kmers_present(ix.kmer_bitmap, ix.kmer_size, rr) ? 3 : 2], 1ull);
+      const bool present = all_kmers_present(ix.kmer_bitmap, ix.kmer_size, rr);
+      atomicAdd(&o.stats[present ? 3 : 2], 1ull);
+      if (o.outcomes) gmx_outcome_put(o, task, present ? GMX_OUTCOME_NO_EXTENSION : GMX_OUTCOME_MISSING_KMER);
     }
   }
 }
@@ -1721,6 +1746,7 @@ __global__ void __launch_bounds__(GMX_BLOCK) gmx_filter_kernel(GmxIndexView ix, 
     ReadRef r = task_read(b, task);
     present = all_kmers_present(ix.kmer_bitmap, ix.kmer_size, r);
     missing = !present;
+    if (o.outcomes) gmx_outcome_put(o, task, present ? GMX_OUTCOME_NO_EXTENSION : GMX_OUTCOME_MISSING_KMER);
   }
   __shared__ uint32_t n_miss, n_noext;
   gmx_block_count(o.stats, 2, missing, &n_miss);
@@ -1770,6 +1796,7 @@ __global__ void __launch_bounds__(GMX_BLOCK) gmx_filter_absent_kernel(GmxIndexVi
       }
     }
     missing = !present;
+    if (o.outcomes) gmx_outcome_put(o, task, present ? GMX_OUTCOME_NO_EXTENSION : GMX_OUTCOME_MISSING_KMER);
   }
   __shared__ uint32_t n_miss, n_noext;
   gmx_block_count(o.stats, 2, missing, &n_miss);
@@ -1823,10 +1850,12 @@ __global__ void __launch_bounds__(GMX_FILTER_LDS_THREADS) gmx_filter_lds_kernel(
        slot += gridDim.x * GMX_FILTER_LDS_THREADS) {
     uint32_t task = (pass ? o.dead2_list : o.dead_list)[slot];
     ReadRef r = task_read(b, task);
-    if (all_kmers_present_planar(gmx_lds, ix.kmer_size, r))
+    const bool present = all_kmers_present_planar(gmx_lds, ix.kmer_size, r);
+    if (present)
       ++c_noext;
     else
       ++c_miss;
+    if (o.outcomes) gmx_outcome_put(o, task, present ? GMX_OUTCOME_NO_EXTENSION : GMX_OUTCOME_MISSING_KMER);
   }
   // one atomic per counter and block
   for (int off = 32; off > 0; off >>= 1) {
@@ -1924,8 +1953,10 @@ __global__ void __launch_bounds__(64) gmx_search_big_kernel(GmxIndexView ix, Bat
     } else if (atomicCAS(&o.error[0], 0u, status) == 0u) {
       o.error[1] = task;
     }
-    if (status == GMX_TASK_MAPPED || status == GMX_TASK_UNMAPPED || status == GMX_STATUS_MISSING_KMER)
+    if (status == GMX_TASK_MAPPED || status == GMX_TASK_UNMAPPED || status == GMX_STATUS_MISSING_KMER) {
       atomicAdd(&o.stats[status == GMX_TASK_MAPPED ? 4 : status == GMX_TASK_UNMAPPED ? 3 : 2], 1ull);  // few tasks: one atomic each
+      if (o.outcomes) gmx_outcome_put(o, task, status == GMX_TASK_MAPPED ? GMX_OUTCOME_MAPPED : status == GMX_TASK_UNMAPPED ? GMX_OUTCOME_NO_EXTENSION : GMX_OUTCOME_MISSING_KMER);
+    }
     o.n_final[task] = nf;
     g.n_final[slot] = nf;
     g.task_of_slot[slot] = task;
@@ -2056,6 +2087,7 @@ __global__ void __launch_bounds__(64) gmx_search_split_kernel(GmxIndexView ix, B
     uint32_t status = GMX_TASK_MAPPED;
     if (total == 0) status = all_kmers_present(ix.kmer_bitmap, ix.kmer_size, r) ? GMX_TASK_UNMAPPED : GMX_STATUS_MISSING_KMER;
     atomicAdd(&o.stats[status == GMX_TASK_MAPPED ? 4 : status == GMX_TASK_UNMAPPED ? 3 : 2], 1ull);
+    if (o.outcomes) gmx_outcome_put(o, task, status == GMX_TASK_MAPPED ? GMX_OUTCOME_MAPPED : status == GMX_TASK_UNMAPPED ? GMX_OUTCOME_NO_EXTENSION : GMX_OUTCOME_MISSING_KMER);
     o.n_final[task] = total;
     g.n_final[slot] = total;
     g.task_of_slot[slot] = task;

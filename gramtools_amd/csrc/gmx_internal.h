@@ -40,6 +40,7 @@ struct GmxEngineRaw {
   bool log_sites;     // the index has sites that use the grouped log
 };
 void gmx_engine_raw(gmx_engine *e, GmxEngineRaw *out);
+uint64_t gmx_engine_outcome_epoch(const gmx_engine *e);  // resets of the outcome buffer so far (gmx_group's ledger)
 // the engine's grouped log as counted records (gmx.h: gmx_coverage_fetch_grouped_log); import adds records to the
 // engine's host-side totals, after emptying them when `replace`
 int gmx_engine_log_export(gmx_engine *e, std::vector<uint32_t> &out);

@@ -260,7 +260,40 @@ int gmx_exchange_peer(std::vector<Member> &ms) {
 struct gmx_group {
   std::vector<Member> ms;
   bool use_rccl = false;
+  // Per-read outcomes: which member recorded which range of the reads the group's feeds were handed, in hand-over order (the
+  // feeds deal contiguous ranges of the read index). Valid while no member's outcome buffer has been reset since (epochs).
+  struct OutcomeRange { uint64_t first, count; size_t member; uint64_t member_first; };
+  std::vector<OutcomeRange> ranges;
+  uint64_t n_outcomes = 0, epochs = 0;
 };
+static uint64_t group_epochs(const gmx_group *g) {
+  uint64_t s = 0;
+  for (auto const &m : g->ms) s += gmx_engine_outcome_epoch(m.e);
+  return s;
+}
+static void group_ledger_sync(gmx_group *g) {  // a member was reset: the ranges before are gone with its bytes
+  const uint64_t now = group_epochs(g);
+  if (now != g->epochs) {
+    g->ranges.clear();
+    g->n_outcomes = 0;
+    g->epochs = now;
+  }
+}
+// around a feed: what every member's count was before it, and the ranges the members recorded (member order = read order)
+static std::vector<uint64_t> group_counts(gmx_group *g) {
+  group_ledger_sync(g);
+  std::vector<uint64_t> c;
+  for (auto const &m : g->ms) c.push_back((uint64_t)std::max<int64_t>(gmx_engine_outcome_count(m.e), 0));
+  return c;
+}
+static void group_note(gmx_group *g, const std::vector<uint64_t> &before) {
+  for (size_t i = 0; i < g->ms.size(); ++i) {
+    const uint64_t now = (uint64_t)std::max<int64_t>(gmx_engine_outcome_count(g->ms[i].e), 0);
+    if (now <= before[i]) continue;
+    g->ranges.push_back({g->n_outcomes, now - before[i], i, before[i]});
+    g->n_outcomes += now - before[i];
+  }
+}
 
 struct gmx_comm {
   Member m;
@@ -369,6 +402,8 @@ int gmx_group_map_reads_host(gmx_group *g, const uint8_t *reads, const uint64_t 
     return GMX_EINVAL;
   }
   const size_t n = g->ms.size();
+  const std::vector<uint64_t> recorded = group_counts(g);
+  struct Note { gmx_group *g; const std::vector<uint64_t> &b; ~Note() { try { group_note(g, b); } catch (...) {} } } note{g, recorded};
   if (n == 1) return gmx_map_reads_host(g->ms[0].e, reads, offsets, seeds, n_reads);
   std::vector<int> rcs(n, GMX_OK);
   std::vector<std::string> errs(n);
@@ -404,6 +439,8 @@ int gmx_group_map_reads_packed_host(gmx_group *g, const uint64_t *planes, const 
     return GMX_EINVAL;
   }
   const size_t n = g->ms.size();
+  const std::vector<uint64_t> recorded = group_counts(g);
+  struct Note { gmx_group *g; const std::vector<uint64_t> &b; ~Note() { try { group_note(g, b); } catch (...) {} } } note{g, recorded};
   if (n == 1) return gmx_map_reads_packed_host(g->ms[0].e, planes, offsets, uniform_len, seeds, skip, n_reads);
   if (!planes || !seeds || (!offsets && !uniform_len)) {
     gmx_set_error("gmx_group_map_reads_packed_host: null argument");
@@ -459,6 +496,35 @@ int gmx_group_map_reads_packed_host(gmx_group *g, const uint64_t *planes, const 
     }
   return GMX_OK;
 } GMX_GUARD_INT("gmx_group_map_reads_packed_host")
+
+int64_t gmx_group_outcome_count(gmx_group *g) try {
+  if (!g) {
+    gmx_set_error("null group");
+    return GMX_EINVAL;
+  }
+  group_ledger_sync(g);
+  return (int64_t)g->n_outcomes;
+} GMX_GUARD_INT("gmx_group_outcome_count")
+
+int gmx_group_fetch_outcomes(gmx_group *g, uint64_t first, uint64_t n, uint8_t *out) try {
+  if (!g || (n && !out)) {
+    gmx_set_error("gmx_group_fetch_outcomes: null argument");
+    return GMX_EINVAL;
+  }
+  group_ledger_sync(g);
+  if (first > g->n_outcomes || n > g->n_outcomes - first) {
+    gmx_set_error("gmx_group_fetch_outcomes: reads " + std::to_string(first) + " .. " + std::to_string(first + n) + " of " +
+                  std::to_string(g->n_outcomes) + " recorded");
+    return GMX_EINVAL;
+  }
+  for (auto const &r : g->ranges) {  // (the exchange is not involved: every member holds its own reads' bytes)
+    const uint64_t lo = std::max(first, r.first), hi = std::min(first + n, r.first + r.count);
+    if (lo >= hi) continue;
+    const int rc = gmx_engine_fetch_outcomes(g->ms[r.member].e, r.member_first + (lo - r.first), hi - lo, out + (lo - first));
+    if (rc) return rc;
+  }
+  return GMX_OK;
+} GMX_GUARD_INT("gmx_group_fetch_outcomes")
 
 int gmx_group_sync_uploads(gmx_group *g) try {
   if (!g) {

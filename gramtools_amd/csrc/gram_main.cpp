@@ -73,7 +73,13 @@ const char *kGenotypeHelp =
     "  --samples_list arg          many samples in one call (engine extension): a file with one line per sample,\n"
     "                              tab-separated: sample_id, genotype_dir, reads file(s). Replaces --reads / --sample_id /\n"
     "                              --genotype_dir. The index is loaded and uploaded once; every sample's files are those of\n"
-    "                              a call of its own with the same --seed\n";
+    "                              a call of its own with the same --seed\n"
+    "  --read_outcomes             what became of every read (engine extension): writes genotype_dir/read_outcomes.bin — a\n"
+    "                              16-byte header (\"GMXO\", uint32 version 1, uint64 read count, little-endian), then one\n"
+    "                              byte per read in the order of the reads files: bits 0-1 the read as given, bits 2-3 its\n"
+    "                              reverse complement (0 skipped, 1 a k-mer not in the index, 2 no exact mapping, 3 exactly\n"
+    "                              mapped), bits 4 / 5 that orientation had several mapping instances to draw from — and\n"
+    "                              read_outcomes.json, the count of every byte value\n";
 
 [[noreturn]] void die(const std::string &msg, int code = 1) {
   std::cout << msg << std::endl;
@@ -2182,6 +2188,19 @@ int run_genotype(const Args &a) {
   }
   phase("engines created (HIP start-up, index upload)");
   gmx_engine *eng = gmx_group_engine(grp, 0);  // after the exchange every engine holds the totals: engine 0 is read back
+  // --read_outcomes: every engine keeps its reads' outcome bytes; which engine took which reads of the files, in file order,
+  // is noted here call by call (a chunk of a device route goes to one engine, a block of the host readers to the group)
+  const bool read_outcomes = a.has("read_outcomes");
+  struct OutcomeSeg { int engine; uint64_t first, n; };  // engine -1: reads first .. first + n of the group's feeds
+  std::vector<OutcomeSeg> outcome_segs;
+  if (read_outcomes)
+    for (int d = 0; d < gmx_group_size(grp); ++d) GMX_CHECK(gmx_engine_record_outcomes(gmx_group_engine(grp, d), 1));
+  auto note_outcomes = [&](int engine, uint64_t n) {  // BEFORE the call that hands n reads to `engine` (or to the group)
+    if (!read_outcomes || n == 0) return;
+    const int64_t at = engine < 0 ? gmx_group_outcome_count(grp) : gmx_engine_outcome_count(gmx_group_engine(grp, engine));
+    if (at < 0) die(std::string("gram: read outcomes: ") + gmx_last_error());
+    outcome_segs.push_back(OutcomeSeg{engine, (uint64_t)at, n});
+  };
   // workspace for the calls the feed will make (a block of a reads file per call, at most 1 M reads per engine)
   for (int d = 0; d < gmx_group_size(grp); ++d) GMX_CHECK(gmx_engine_reserve_packed(gmx_group_engine(grp, d), info.is_nested ? 4u << 20 : 3u << 19 /* (a decoded BGZF chunk of 150 bp reads: 1.46 M) */, ((info.is_nested ? 24ull : 6ull) << 20) + 64));
   if (prewarm.joinable()) prewarm.join();
@@ -2205,6 +2224,7 @@ int run_genotype(const Args &a) {
   phase("base error rate of the first 10 000 reads");
   if (sample_i > 0) {  // the accumulators and read counters of the sample before
     for (int d = 0; d < gmx_group_size(grp); ++d) GMX_CHECK(gmx_engine_reset(gmx_group_engine(grp, d)));
+    outcome_segs.clear();
     g_feed = FeedTimes{};
   }
   std::cout << "Running quasimap" << std::endl;
@@ -2259,6 +2279,7 @@ int run_genotype(const Args &a) {
         feed_trace("  chunk's seed buffer ready");
         seed_stream.copy(file_base + in_file, n, sd.data());
         feed_trace("  chunk's seeds copied");
+        note_outcomes((int)k, n);
         if (res.uniform_len) {
           GMX_CHECK(gmx_map_reads_packed_device(ek, res.d_planes, nullptr, res.uniform_len, sd.data(), res.any_skip ? res.d_skip : nullptr, n));
         } else {
@@ -2319,6 +2340,7 @@ int run_genotype(const Args &a) {
       // the block goes up as it is — bit planes from page-locked memory, chunk by chunk beside the kernels (the call returns
       // once everything is enqueued) — and may be overwritten by the parser as soon as its uploads are done
       if (n) {
+        note_outcomes(-1, n);
         GMX_CHECK(gmx_group_map_reads_packed_host(grp, block.planes.data() + block.pair_of(first), block.uniform_len ? nullptr : block.offsets.data() + first,
                                                   block.uniform_len, block.seeds.data(), block.any_skip ? block.skip.data() + first : nullptr, n));
         GMX_CHECK(gmx_group_sync_uploads(grp));
@@ -2344,6 +2366,7 @@ int run_genotype(const Args &a) {
     auto flush = [&]() {
       if (offsets.size() > 1) {
         if (bases.empty()) bases.push_back(0);
+        note_outcomes(-1, offsets.size() - 1);
         GMX_CHECK(gmx_group_map_reads_host(grp, bases.data(), offsets.data(), seeds.data(), offsets.size() - 1));
       }
       bases.clear();
@@ -2400,6 +2423,45 @@ int run_genotype(const Args &a) {
 
   // The three coverage files and read_stats.json are written on a thread of their own, beside the genotyping model below
   // (round 5: at configs[1] they were 42 ms of a call whose mapping takes 24; nothing below reads what they write).
+  if (read_outcomes) {  // G/read_outcomes.bin + .json: the engines' bytes put together in the order of the reads files
+    std::vector<uint8_t> bytes(std::max<uint64_t>(total_reads, 1));
+    uint64_t at = 0;
+    for (auto const &sg : outcome_segs) {
+      if (at + sg.n > total_reads) die("gram: read outcomes: more bytes than reads");
+      if (sg.engine < 0)
+        GMX_CHECK(gmx_group_fetch_outcomes(grp, sg.first, sg.n, bytes.data() + at));
+      else
+        GMX_CHECK(gmx_engine_fetch_outcomes(gmx_group_engine(grp, sg.engine), sg.first, sg.n, bytes.data() + at));
+      at += sg.n;
+    }
+    if (at != total_reads) die("gram: read outcomes: " + std::to_string(at) + " bytes for " + std::to_string(total_reads) + " reads");
+    const std::string bin_path = join(run_dir, "read_outcomes.bin"), json_path = join(run_dir, "read_outcomes.json");
+    {
+      std::ofstream o(bin_path, std::ios::binary);
+      unsigned char header[16] = {'G', 'M', 'X', 'O', 1, 0, 0, 0};
+      for (int i = 0; i < 8; ++i) header[8 + i] = (unsigned char)((total_reads >> (8 * i)) & 0xFF);
+      o.write(reinterpret_cast<const char *>(header), 16);
+      o.write(reinterpret_cast<const char *>(bytes.data()), (std::streamsize)total_reads);
+      close_checked(o, bin_path);
+    }
+    uint64_t by_value[256] = {0}, by_code[4] = {0};
+    for (uint64_t i = 0; i < total_reads; ++i) {
+      ++by_value[bytes[i]];
+      ++by_code[bytes[i] & 3u];
+      ++by_code[(bytes[i] >> 2) & 3u];
+    }
+    std::ofstream o(json_path);
+    o << "{\"reads\":" << total_reads << ",\"tasks\":{\"skipped\":" << by_code[0] << ",\"missing_kmer\":" << by_code[1] << ",\"no_extension\":" << by_code[2]
+      << ",\"exact_mapped\":" << by_code[3] << "},\"bytes\":{";
+    bool first_value = true;
+    for (int v = 0; v < 256; ++v)
+      if (by_value[v]) {
+        o << (first_value ? "" : ",") << "\"" << v << "\":" << by_value[v];
+        first_value = false;
+      }
+    o << "}}\n";
+    close_checked(o, json_path);
+  }
   std::string rs_path = join(run_dir, "read_stats.json");
   std::cout << "Writing read stats to " << rs_path << std::endl;
   std::thread cov_writer([&]() {

@@ -542,6 +542,27 @@ class Quasimapper:
     def sync(self):
         check(self.lib.gmx_engine_sync(self.h))
 
+    def record_outcomes(self, on: bool = True):
+        """From the next mapping call on every read leaves one outcome byte (gmx_engine_record_outcomes); see outcomes()."""
+        check(self.lib.gmx_engine_record_outcomes(self.h, 1 if on else 0))
+
+    def outcome_count(self) -> int:
+        """Reads recorded since the last reset."""
+        return check(self.lib.gmx_engine_outcome_count(self.h))
+
+    def outcomes(self, first: int = 0, n: int = None) -> np.ndarray:
+        """The outcome bytes of reads first .. first + n (default: all recorded), in the order the reads were handed over:
+        bits 0-1 the forward task's code, 2-3 the reverse-complement task's (0 skipped, 1 missing k-mer, 2 no exact mapping,
+        3 exactly mapped), bit 4 / 5 that task's selection drew among several mapping instances (gmx_engine_fetch_outcomes)."""
+        count = self.outcome_count()
+        if n is None:
+            n = count - first
+        if first < 0 or n < 0 or first + n > count:
+            raise ValueError(f"outcomes: reads {first} .. {first + n} of {count} recorded")
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        check(self.lib.gmx_engine_fetch_outcomes(self.h, first, n, _p(out, C.c_uint8)))
+        return out[:n]
+
     def enable_timing(self, on=True):
         check(self.lib.gmx_engine_enable_timing(self.h, 1 if on else 0))
 
@@ -878,6 +899,25 @@ class QuasimapperGroup:
 
     def allreduce(self):
         check(self.lib.gmx_group_allreduce(self.h))
+
+    def record_outcomes(self, on: bool = True):
+        """Per-read outcomes on every member (Quasimapper.record_outcomes); see outcomes()."""
+        for i in range(self.lib.gmx_group_size(self.h)):
+            check(self.lib.gmx_engine_record_outcomes(C.c_void_p(self.lib.gmx_group_engine(self.h, i)), 1 if on else 0))
+
+    def outcome_count(self) -> int:
+        return check(self.lib.gmx_group_outcome_count(self.h))
+
+    def outcomes(self, first: int = 0, n: int = None) -> np.ndarray:
+        """Outcome bytes of the reads handed to the group's feeds, in that order (gmx_group_fetch_outcomes)."""
+        count = self.outcome_count()
+        if n is None:
+            n = count - first
+        if first < 0 or n < 0 or first + n > count:
+            raise ValueError(f"outcomes: reads {first} .. {first + n} of {count} recorded")
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        check(self.lib.gmx_group_fetch_outcomes(self.h, first, n, _p(out, C.c_uint8)))
+        return out[:n]
 
     def coverage(self, member: int = 0) -> Coverage:
         """Coverage held by engine `member` (after :meth:`allreduce`: the totals of the whole job, on every member)."""

@@ -464,6 +464,7 @@ typedef struct gmx_queue_counts {
   uint64_t huge_cover;        /* tasks whose selection scratch the last tier sized from the heap */
   uint64_t log_replays;       /* since the engine was created: rounds in which entries that found the grouped log full were redone */
   uint64_t log_replayed_entries; /* ... and how many entries those rounds redid */
+  uint64_t overflow_split;    /* overflow tasks whose share of a slot under the 16-lane split search did not suffice: redone by one lane with a whole slot */
 } gmx_queue_counts;
 int gmx_engine_queue_counts(gmx_engine *e, gmx_queue_counts *out);
 
@@ -502,6 +503,25 @@ int gmx_coverage_reduce_end(gmx_engine *e, void *hip_stream);
  * saturates at 65535 (allele_base.cpp:239). gmx_finalize_u16 applies them. */
 int gmx_coverage_fetch(gmx_engine *e, uint32_t *allele_sum, uint32_t *per_base, uint32_t *grouped_dense,
                        gmx_stats *stats);
+
+/* Per-read outcomes: what became of every read, one byte each (off by default; nothing changes while it is off).
+ *   bits 0-1  the forward task            bits 2-3  the reverse-complement task (0 when the engine maps forward only)
+ *   bit 4 / 5 the forward / reverse-complement task's selection drew among more than one mapping instance
+ *   bits 6-7  zero
+ * Task codes: 0 skipped (shorter than k, or unencodable), 1 a k-mer of the read is not in the index, 2 no exact mapping,
+ * 3 exactly mapped: over all reads the codes add up to the four counters of gmx_stats behind all_reads_count. While recording
+ * is on every mapping call, of every feed, appends its reads' bytes to a buffer the engine owns, in the order the reads were
+ * handed over since the last gmx_engine_reset / gmx_engine_reset_async (which empty it), whichever of the engine's two
+ * workspaces ran a launch. gmx_engine_fetch_outcomes waits for the engine's work and copies bytes first .. first + n. */
+#define GMX_OUTCOME_SKIPPED 0
+#define GMX_OUTCOME_MISSING_KMER 1
+#define GMX_OUTCOME_NO_EXTENSION 2
+#define GMX_OUTCOME_MAPPED 3
+#define GMX_OUTCOME_MULTI_FORWARD 0x10
+#define GMX_OUTCOME_MULTI_REVERSE 0x20
+int gmx_engine_record_outcomes(gmx_engine *e, int on);
+int64_t gmx_engine_outcome_count(gmx_engine *e);
+int gmx_engine_fetch_outcomes(gmx_engine *e, uint64_t first, uint64_t n, uint8_t *out);
 /* Grouped counts of sites with more than 8 alleles (grouped_allele_counts.cpp:17-49 for sites without dense slots).
  * Returns the number of uint32 words of the log (and copies it when it fits cap_words). The log is a sequence of records
  *   [site_index, n_ids, ids...]                                     worth +1, or
@@ -593,6 +613,11 @@ int gmx_group_map_reads_packed_host(gmx_group *g, const uint64_t *planes, const 
                                     const uint32_t *seeds, const uint8_t *skip, uint64_t n_reads);
 int gmx_group_sync_uploads(gmx_group *g);
 int gmx_group_allreduce(gmx_group *g); /* the exchange; synchronises every engine first */
+/* Per-read outcomes of a group (gmx_engine_record_outcomes on every member): the group's feeds deal contiguous ranges of the
+ * read index to the members, and these put the members' ranges together again — reads in the order they were handed to
+ * gmx_group_map_reads_* since the members' last reset. The exchange is not involved. */
+int64_t gmx_group_outcome_count(gmx_group *g);
+int gmx_group_fetch_outcomes(gmx_group *g, uint64_t first, uint64_t n, uint8_t *out);
 
 typedef struct gmx_comm gmx_comm; /* one engine per PROCESS (torch.distributed.run, mpirun, ...): rank 0 makes the id,
                                      the launcher's own channel broadcasts its 128 bytes, every rank creates its comm */
