@@ -1695,6 +1695,7 @@ __global__ void __launch_bounds__(256) gmx_bam_pack_kernel(const uint8_t *text, 
 struct GzPiece {
   uint32_t start, end;  // bits within the chunk's bytes: where decoding started, where it stopped
   uint32_t n_sym, flags, n_ends, text_off;
+  uint32_t need, tail;  // bytes of the open member its matches need in front of the piece; symbols behind its last member end (all, when none)
   uint32_t end_at[GZ_ENDS], end_crc[GZ_ENDS], end_isize[GZ_ENDS];  // member ends: symbol index, the trailer's CRC-32 and ISIZE
   uint32_t seg_crc[GZ_ENDS + 1], seg_pow[GZ_ENDS + 1];             // the text between them: CRC register from 0, x^(8 length)
 };
@@ -1706,6 +1707,7 @@ struct GzState {  // one per ingest: where the stream stands between chunks
   uint32_t flags;            // GMX_INGEST_* of the chunk
   uint32_t n_pieces;         // pieces in the chunk's chain
   uint32_t repairs;          // pieces decoded again from their predecessor's end, since the ingest was created
+  uint32_t open;             // text of the open member at the chunk's end, saturated at GZ_WIN (run_len wraps with ISIZE: not that)
 };
 struct GzArgs {
   const uint32_t *comp;
@@ -1770,6 +1772,7 @@ __device__ __forceinline__ uint16_t gz_load_coherent(const ing_g16 *p) { return 
 
 struct GzDone {  // what gz_decode leaves (also in a.pieces[pi]; the link kernel goes on with these, not with its own stores)
   uint32_t flags, end, n_sym;
+  uint32_t need, tail, n_ends;  // (GzPiece)
 };
 // Piece `pi` from bit `start` until a block ends at or beyond `stop` (or the stream ends). header_first: a member header stands at
 // `start` (the file's first). trial: the first block must pass the block finder's tests (else the result is 0 and nothing is
@@ -1789,6 +1792,8 @@ __device__ __forceinline__ GzDone gz_decode(WaveLds &L, const GzArgs &a, uint32_
   const uint32_t cap = uni(a.cap), stop = uni(gz_stop_bit(a, pi)), nb = uni(a.n_bytes), fin = uni(a.final_chunk);
   uint32_t out_pos = 0, flushed = 0, n_ends = 0, flags = GZP_FOUND, pos = start;
   int mstart = -(int)GZ_WIN;  // references may not reach below this (a member's first symbol: an empty window)
+  int need = 0;               // how far the matches reach in front of the piece: the link kernel knows how much of the member lies there
+  uint32_t last_end = 0;      // out_pos at the piece's last member end
   auto ring_reset = [&]() {  // the slots of positions [-1024, 0): placeholders for the window in front of the piece
     for (uint32_t k = lane; k < GZ_RING; k += 64u) ring[k] = (uint16_t)(256u + GZ_WIN - GZ_RING + k);
   };
@@ -1917,6 +1922,7 @@ __device__ __forceinline__ GzDone gz_decode(WaveLds &L, const GzArgs &a, uint32_
           } else if (__builtin_expect(out_pos + len > cap, 0)) {
             stop_c = 3u;
           } else {
+            need = max(need, (int)(dist - out_pos));
             copy_match(len, dist);
           }
         }
@@ -1953,10 +1959,11 @@ __device__ __forceinline__ GzDone gz_decode(WaveLds &L, const GzArgs &a, uint32_
           ok = (len ^ nlen) == 0xFFFFu;
         }
       }
-      if (!ok) return GzDone{0u, 0u, 0u};
+      if (!ok) return GzDone{0u, 0u, 0u, 0u, 0u, 0u};
       if (late) {  // test hook: a wrong (later) start, the link kernel has to repair it
         start = pos;
         out_pos = flushed = 0;
+        need = 0;
         ring_reset();
       }
     }
@@ -1982,6 +1989,7 @@ __device__ __forceinline__ GzDone gz_decode(WaveLds &L, const GzArgs &a, uint32_
         pc->end_isize[n_ends] = isize;
       }
       ++n_ends;
+      last_end = out_pos;
       at += 8u;
       pos = at * 8u;
       if (at + 3u <= nb && uni(gz_byte(a, at) | gz_byte(a, at + 1u) << 8 | gz_byte(a, at + 2u) << 16) == 0x088b1fu) {
@@ -2013,8 +2021,10 @@ done:
     pc->n_sym = out_pos;
     pc->flags = flags;
     pc->n_ends = n_ends;
+    pc->need = (uint32_t)need;
+    pc->tail = out_pos - last_end;
   }
-  return GzDone{uni(flags), uni(pos), uni(out_pos)};
+  return GzDone{uni(flags), uni(pos), uni(out_pos), uni((uint32_t)need), uni(out_pos - last_end), uni(n_ends)};
 }
 
 // one wavefront per piece: its start (known, or searched), then its symbols
@@ -2077,6 +2087,7 @@ __global__ void __launch_bounds__(64) gmx_gz_link_kernel(GzArgs a, uint64_t max_
       st->eos = 0;
       st->run_crc = 0xFFFFFFFFu;
       st->run_len = 0;
+      st->open = 0;
     }
     __syncthreads();
   }
@@ -2087,12 +2098,13 @@ __global__ void __launch_bounds__(64) gmx_gz_link_kernel(GzArgs a, uint64_t max_
     if (lane == 0) st->bit = uni(st->bit) > a.n_own * 8u ? uni(st->bit) - a.n_own * 8u : 0u;
   } else {
     uint32_t prev_end = 0, pf = 0;
+    uint32_t open = a.fresh ? 0u : uni(st->open);  // text of the open member in front of the piece, saturated at 32 KB: all a match can reach
     for (uint32_t i = 0; i < a.n_pieces; ++i) {
       GzPiece *const pc = a.pieces + i;
-      GzDone d{uni(pc->flags), uni(pc->end), uni(pc->n_sym)};  // (written by gmx_gz_decode_kernel)
+      GzDone d{uni(pc->flags), uni(pc->end), uni(pc->n_sym), uni(pc->need), uni(pc->tail), uni(pc->n_ends)};  // (written by gmx_gz_decode_kernel)
       if (i > 0) {
         if (prev_end >= gz_stop_bit(a, i)) {  // a block of the piece before reaches over this piece's span: nothing left here
-          d = GzDone{GZP_FOUND, prev_end, 0u};
+          d = GzDone{GZP_FOUND, prev_end, 0u, 0u, 0u, 0u};
           if (lane == 0) {
             pc->start = pc->end = prev_end;
             pc->n_sym = pc->n_ends = 0;
@@ -2110,7 +2122,11 @@ __global__ void __launch_bounds__(64) gmx_gz_link_kernel(GzArgs a, uint64_t max_
       if (pf & GZP_CAPPED) flags |= GMX_INGEST_GZ_PIECE_BOUND;
       if (pf & GZP_OVERRUN) flags |= a.final_chunk ? GMX_INGEST_BAD_MEMBER : GMX_INGEST_GZ_LOOKAHEAD;
       if (pf & GZP_ENDS) flags |= GMX_INGEST_GZ_MEMBER_ENDS;
+      // a match may not reach in front of its member's first byte: within a piece mstart sees it, across pieces only the chain
+      // knows how much of the member lies in front (the windows hold the text of earlier members, or zeros, there)
+      if (!(pf & GZP_BAD) && d.need > open) flags |= GMX_INGEST_BAD_MEMBER;
       if (flags) break;
+      open = min(d.n_ends ? d.tail : open + d.tail, GZ_WIN);
       if (lane == 0) pc->text_off = (uint32_t)text;
       text += d.n_sym;
       prev_end = d.end;
@@ -2127,6 +2143,7 @@ __global__ void __launch_bounds__(64) gmx_gz_link_kernel(GzArgs a, uint64_t max_
         flags = GMX_INGEST_BAD_MEMBER;  // the stream stops without its last member's trailer: truncated
       } else if (lane == 0) {
         st->bit = prev_end - a.n_own * 8u;
+        st->open = open;
       }
       if (text > max_text) flags |= GMX_INGEST_GZ_TEXT_LIMIT;
     }

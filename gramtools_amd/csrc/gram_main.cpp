@@ -83,7 +83,11 @@ const char *kGenotypeHelp =
 
 [[noreturn]] void die(const std::string &msg, int code = 1) {
   std::cout << msg << std::endl;
-  exit(code);
+  // _exit, as at the end of a run: exit() runs the static destructors, the HIP runtime's among them, and run_genotype's
+  // hip_warm thread may still be bringing that runtime up (a refused reads file ends the run within its first milliseconds)
+  std::cerr.flush();
+  fflush(nullptr);
+  _exit(code);
 }
 
 void mkdirs(const std::string &path) {

@@ -25,9 +25,10 @@ def member(data: bytes, level=6, strategy=zlib.Z_DEFAULT_STRATEGY, header=GZ_HDR
     return header + body + struct.pack("<II", crc, isize)
 
 
-def decode(data: bytes, chunk=None, look=1 << 18, max_text=8 << 20, cuts=None):
+def decode(data: bytes, chunk=None, look=1 << 18, max_text=8 << 20, cuts=None, allow=0):
     """The file through one Ingest in chunks (of `chunk` bytes, or cut at `cuts`) with `look` bytes of look-ahead: (text of
-    the whole file as the chunks hand it over, the results, the ingest)."""
+    the whole file as the chunks hand it over, the results, the ingest). allow: status bits that do not end it (text that is
+    no FASTQ: the record scan's)."""
     from gramtools_amd import Ingest
     ing = Ingest(max_text_bytes=max_text)
     n = len(data)
@@ -42,7 +43,7 @@ def decode(data: bytes, chunk=None, look=1 << 18, max_text=8 << 20, cuts=None):
         ing.submit_gzip(k % 2, data[c0:c1 if final else min(n, c1 + look)], c1 - c0, final)
         res = ing.wait(k % 2)
         results.append(res)
-        if res.status:
+        if res.status & ~allow:
             return None, results, ing
         t = ing.fetch_text(k % 2)
         text += t[tail:]
