@@ -161,6 +161,8 @@ SYMBOLS = {
     "gmx_engine_record_outcomes": (C.c_int, [_vp, C.c_int]),
     "gmx_engine_outcome_count": (_i64, [_vp]),
     "gmx_engine_fetch_outcomes": (C.c_int, [_vp, _u64, _u64, _u8p]),
+    "gmx_engine_record_strands": (C.c_int, [_vp, C.c_int]),
+    "gmx_coverage_fetch_strand": (C.c_int, [_vp, C.c_int, _u32p, _u32p, _u32p]),
     "gmx_coverage_import_grouped_log": (C.c_int, [_vp, _u32p, _u64, C.c_int]),
     "gmx_grouped_log_merge_gathered": (_i64, [_vp, _vp, C.c_int, _u64, _vp, _u64]),
     "gmx_finalize_u16": (None, [_u32p, _u64, C.c_int]),
@@ -190,6 +192,7 @@ SYMBOLS = {
     "gmx_group_allreduce": (C.c_int, [_vp]),
     "gmx_group_outcome_count": (_i64, [_vp]),
     "gmx_group_fetch_outcomes": (C.c_int, [_vp, _u64, _u64, _u8p]),
+    "gmx_group_record_strands": (C.c_int, [_vp, C.c_int]),
     "gmx_comm_unique_id": (C.c_int, [_u8p]),
     "gmx_comm_create": (C.c_int, [_u8p, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),
     "gmx_comm_destroy": (None, [_vp]),

@@ -19,6 +19,10 @@ struct CoverAcc {
   const uint32_t *status;      // per task, for the read counters tallied by the batch's last launch
   uint32_t n_tasks;
   unsigned long long *stats;   // QuasimapReadsStats counters
+  uint32_t rev_off;            // words from `acc` to the reverse-complement tasks' block (gmx_engine_record_strands); 0: one block
+  // the block a task records into, as its offset in words (a task's orientation is task & 1): `acc` stays wave-uniform, the
+  // offset is 32 bits per lane (profiles/strand_coverage/README.md: what the kernels' registers make of other forms)
+  __device__ __forceinline__ uint32_t off_of(uint32_t task) const { return (task & 1u) ? rev_off : 0u; }
 };
 
 // The grouped log (sites without dense group counters): a task reserves ALL the words it will append with one atomic add,
@@ -69,6 +73,7 @@ struct CoverLogPart {
   }
 #endif
   uint32_t *acc, *log, *log_cursor;
+  uint32_t acc_off;  // the task's block (CoverAcc::off_of), added to every slot
   uint32_t log_cap;
   uint32_t status;
   uint32_t log_at;
@@ -108,12 +113,13 @@ struct CoverLogPart {
   __device__ __forceinline__ void log_grouped_id(int32_t a) { log[log_at++] = (uint32_t)a; }
   __device__ __forceinline__ void log_grouped_end() {}
   __device__ __forceinline__ uint32_t single_loci() const { return GMX_SINGLE_LOCI; }
-  __device__ __forceinline__ void add_allele_sum(uint32_t slot) { atomicAdd(&acc[slot], 1u); }
-  __device__ __forceinline__ void add_per_base(uint32_t slot) { atomicAdd(&acc[slot], 1u); }
-  __device__ __forceinline__ void add_hit(uint32_t slot) { atomicAdd(&acc[slot], 1u); }
-  __device__ __forceinline__ void add_grouped_dense(uint32_t slot) { atomicAdd(&acc[slot], 1u); }
-  __device__ __forceinline__ void add_allele_and_group(uint32_t slot) {  // slot is even: both counters in one 64-bit add
-    atomicAdd(reinterpret_cast<unsigned long long *>(acc + slot), 0x100000001ull);
+  __device__ __forceinline__ uint32_t *block() const { return acc + acc_off; }
+  __device__ __forceinline__ void add_allele_sum(uint32_t slot) { atomicAdd(&block()[slot], 1u); }
+  __device__ __forceinline__ void add_per_base(uint32_t slot) { atomicAdd(&block()[slot], 1u); }
+  __device__ __forceinline__ void add_hit(uint32_t slot) { atomicAdd(&block()[slot], 1u); }
+  __device__ __forceinline__ void add_grouped_dense(uint32_t slot) { atomicAdd(&block()[slot], 1u); }
+  __device__ __forceinline__ void add_allele_and_group(uint32_t slot) {  // slot is even (and so is acc_off): both counters in one 64-bit add
+    atomicAdd(reinterpret_cast<unsigned long long *>(block() + slot), 0x100000001ull);
   }
   __device__ __forceinline__ void fail(uint32_t s) {
     if (status == GMX_TASK_MAPPED || s == GMX_TASK_ERROR) status = s;
@@ -314,6 +320,7 @@ __device__ uint32_t gmx_tail_item(const GmxIndexView &ix, const BatchView &b, co
   env.scratch = scratch;
   env.arena = arena;
   env.acc = acc.acc;
+  env.acc_off = acc.off_of(task);
   env.log = acc.log;
   env.log_cursor = acc.log_cursor;
   env.log_cap = acc.log_cap;
@@ -438,6 +445,7 @@ __global__ void __launch_bounds__(GMX_BLOCK) gmx_cover_kernel(GmxIndexView ix, B
     env.stride = LDS ? LANES : acc.n_lanes_big;
     env.arena = arena;
     env.acc = acc.acc;
+    env.acc_off = acc.off_of(task);
     env.log = acc.log;
     env.log_cursor = acc.log_cursor;
     env.log_cap = acc.log_cap;
@@ -518,6 +526,7 @@ __global__ void __launch_bounds__(GMX_ONE_THREADS) gmx_cover_one_kernel(GmxIndex
         env.scratch = gmx_lds + threadIdx.x;
         env.arena = ts.arena;
         env.acc = acc.acc;
+        env.acc_off = acc.off_of(ts.task);
         env.log = acc.log;
         env.log_cursor = acc.log_cursor;
         env.log_cap = acc.log_cap;
@@ -594,6 +603,7 @@ __global__ void __launch_bounds__(64) gmx_cover_coop_kernel(GmxIndexView ix, Bat
   ce.scratch = gmx_lds + 64u * GmxScratchFixed<CoopItemEnv>::total + grp;
   ce.stride = 4;
   ie.acc = ce.acc = acc.acc;
+  ie.acc_off = ce.acc_off = 0;  // (per task, where the drawn class records: below)
   ie.log = ce.log = acc.log;
   ie.log_cursor = ce.log_cursor = acc.log_cursor;
   ie.log_cap = ce.log_cap = acc.log_cap;
@@ -739,6 +749,7 @@ __global__ void __launch_bounds__(64) gmx_cover_coop_kernel(GmxIndexView ix, Bat
       const uint32_t read = ts.task >> 1;
       const uint32_t len = read_len(b, read);
       ce.arena = ts.arena;
+      ce.acc_off = acc.off_of(ts.task);
       ce.status = GMX_TASK_MAPPED;
       ce.log_at = 0;
       uint32_t n_loci = 0, n_hull = 0;
@@ -840,6 +851,7 @@ __device__ __forceinline__ void gmx_cover_single_rec(const GmxIndexView &ix, con
   CompactEnv env;
   env.rec = o.cover_recs[rec_idx];
   env.acc = acc.acc;
+  env.acc_off = acc.rev_off ? acc.off_of(o.cover_rec_task[rec_idx]) : 0u;  // (a wave-uniform branch: one block, no load)
   env.log = acc.log;
   env.log_cursor = acc.log_cursor;
   env.log_cap = acc.log_cap;
@@ -891,6 +903,7 @@ __global__ void __launch_bounds__(GMX_BLOCK, GMX_JUMP_MIN_BLOCKS) gmx_cover_jump
   CompactEnv env;
   env.rec = o.cover_recs[rec_idx];
   env.acc = acc.acc;
+  env.acc_off = acc.rev_off ? acc.off_of(o.cover_rec_task[rec_idx]) : 0u;  // (a wave-uniform branch: one block, no load)
   env.log = nullptr;
   env.log_cursor = nullptr;
   env.log_cap = 0;

@@ -26,6 +26,10 @@ struct gmx_engine {
   // accumulators
   uint32_t *d_fused = nullptr, *d_limbs = nullptr;  // accumulator block (n_acc words, gmx_types.h) | 32 counter-limb words
   size_t n_fused = 0, n_acc = 0;
+  // Coverage per strand (gmx_engine_record_strands): two accumulator blocks of n_acc words, forward tasks' then reverse-complement
+  // tasks' (CoverAcc::rev_off = n_acc), the limbs behind both: n_fused = 2 * n_acc + 32. Off: one block, rev_off = 0.
+  bool record_strands = false;
+  bool recorded = false;  // something may have been added to the block since it was last zeroed (launches, an exchange)
   std::vector<uint32_t> phys_allele, phys_pb, phys_grouped;  // logical slot -> slot of the block (gmx_coverage_fetch)
   std::vector<uint32_t> hit_fix;                             // hit counters and the logical slots they count for
   unsigned long long *d_stats = nullptr;  // with d_log_cursor behind the coverage block: one memset resets all of it
@@ -474,6 +478,7 @@ static void gmx_dev_index_release(GmxDeviceIndex *d) {
 }
 
 static int engine_create(const gmx_index *ixh, const gmx_engine_opts *opts_in, gmx_engine *primary, gmx_engine **out);
+static int set_record_strands(gmx_engine *e, bool on);
 int gmx_engine_create(const gmx_index *ixh, const gmx_engine_opts *opts_in, gmx_engine **out) try {
   int rc = engine_create(ixh, opts_in, nullptr, out);
   if (rc) return rc;
@@ -494,6 +499,13 @@ int gmx_engine_create(const gmx_index *ixh, const gmx_engine_opts *opts_in, gmx_
       (void)hipGetLastError();  // (no room for a second workspace: one batch at a time, as before)
     }
   }
+  // MEASUREMENT HOOK ONLY (profiles/strand_coverage: the cost of two blocks in an unchanged benchmark): nothing reads them apart
+  if (const char *rs = getenv("GMX_RECORD_STRANDS"))
+    if (atoi(rs) != 0 && (rc = set_record_strands(e, true))) {
+      gmx_engine_destroy(e);
+      *out = nullptr;
+      return rc;
+    }
   return GMX_OK;
 } GMX_GUARD_INT("gmx_engine_create")
 
@@ -844,6 +856,7 @@ int gmx_engine_reset(gmx_engine *e) try {
   e->log_counts.clear();
   e->log_known = e->log_reads_since = 0;
   e->log_state_pending = false;
+  e->recorded = false;
   return GMX_OK;
 } GMX_GUARD_INT("gmx_engine_reset")
 
@@ -864,6 +877,7 @@ int gmx_engine_reset_async(gmx_engine *e, void *hip_stream) try {
   e->log_counts.clear();  // what earlier batches left in the device log goes with the cursor
   e->log_known = e->log_reads_since = 0;
   e->log_state_pending = false;
+  e->recorded = false;
   return GMX_OK;
 } GMX_GUARD_INT("gmx_engine_reset_async")
 
@@ -1101,6 +1115,7 @@ static int launch_batch(gmx_engine *e, const BatchInput &in, hipStream_t stream)
   o.stats = e->d_stats;
   {
     gmx_engine *own = e->owner ? e->owner : e;
+    own->recorded = true;
     if (own->record_outcomes) {  // (room was made in ensure_batch_capacity)
       o.outcomes = own->d_outcomes;
       o.outcome_base = own->outcome_count;
@@ -1162,7 +1177,8 @@ static int launch_batch(gmx_engine *e, const BatchInput &in, hipStream_t stream)
   HIP_TRY(hipEventRecord(e->ev_fork, stream));
   HIP_TRY(hipStreamWaitEvent(e->side_stream, e->ev_fork, 0));
   CoverAcc acc{e->d_fused, e->d_log, e->d_log_cursor, e->log_cap, e->d_scratch_big, e->cover_big_lanes, e->opts.rng_mode,
-               e->log_sites ? 1u : 0u, e->d_heap, e->heap_words, e->d_status, (uint32_t)n_reads * 2u, e->d_stats};
+               e->log_sites ? 1u : 0u, e->d_heap, e->heap_words, e->d_status, (uint32_t)n_reads * 2u, e->d_stats,
+               (e->owner ? e->owner : e)->record_strands ? (uint32_t)e->n_acc : 0u};
   if (seeded) {  // what gmx_seed_kernel sent to the large-capacity pass (reads in repeats), and its coverage: on side 2
     HIP_TRY(hipStreamWaitEvent(e->side2_stream, e->ev_fork, 0));
     const InstPools pools{0};
@@ -2036,6 +2052,7 @@ int gmx_coverage_reduce_begin(gmx_engine *e, void *hip_stream) try {
     int trc = twin_join(e, (hipStream_t)hip_stream);  // (the exchange reads what the twin's batches record)
     if (trc) return trc;
   }
+  e->recorded = true;  // (what the exchange adds to the block)
   hipLaunchKernelGGL(gmx_stats_limbs_kernel, dim3(1), dim3(64), 0, (hipStream_t)hip_stream, e->d_stats, e->d_limbs, 0);
   HIP_TRY(hipGetLastError());
   return GMX_OK;
@@ -2056,11 +2073,20 @@ int gmx_coverage_reduce_end(gmx_engine *e, void *hip_stream) try {
   return GMX_OK;
 } GMX_GUARD_INT("gmx_coverage_reduce_end")
 
-int gmx_coverage_fetch(gmx_engine *e, uint32_t *allele_sum, uint32_t *per_base, uint32_t *grouped, gmx_stats *stats) try {
-  if (!e) {
-    gmx_set_error("null engine");
-    return GMX_EINVAL;
+// one accumulator block -> the three logical arrays, ADDED to them (the gather of gmx_coverage_fetch; any pointer may be null)
+static void gather_block(const gmx_engine *e, const uint32_t *block, uint32_t *allele_sum, uint32_t *per_base, uint32_t *grouped) {
+  if (allele_sum) for (size_t i = 0; i < e->phys_allele.size(); ++i) allele_sum[i] += block[e->phys_allele[i]];
+  if (per_base) for (size_t i = 0; i < e->phys_pb.size(); ++i) per_base[i] += block[e->phys_pb[i]];
+  if (grouped) for (size_t i = 0; i < e->phys_grouped.size(); ++i) grouped[i] += block[e->phys_grouped[i]];
+  for (size_t i = 0; i + 3 < e->hit_fix.size(); i += 4) {  // a hit = one each of allele-sum, group {allele} and the base
+    const uint32_t hits = block[e->hit_fix[i]];
+    if (allele_sum) allele_sum[e->hit_fix[i + 1]] += hits;
+    if (grouped) grouped[e->hit_fix[i + 2]] += hits;
+    if (per_base) per_base[e->hit_fix[i + 3]] += hits;
   }
+}
+// blocks [first, first + count) of the engine, gathered and added up (uint32 wrap) into zeroed outputs
+static int fetch_blocks(gmx_engine *e, size_t first, size_t count, uint32_t *allele_sum, uint32_t *per_base, uint32_t *grouped) {
   {
     int frc = flush_reset(e);
     if (frc) return frc;
@@ -2068,16 +2094,24 @@ int gmx_coverage_fetch(gmx_engine *e, uint32_t *allele_sum, uint32_t *per_base, 
   }
   HIP_TRY(hipSetDevice(e->opts.device));
   HIP_TRY(hipDeviceSynchronize());
-  std::vector<uint32_t> block(std::max<size_t>(e->n_acc, 1));
-  if (e->n_acc) HIP_TRY(hipMemcpy(block.data(), e->d_fused, e->n_acc * 4, hipMemcpyDeviceToHost));
-  if (allele_sum) for (size_t i = 0; i < e->phys_allele.size(); ++i) allele_sum[i] = block[e->phys_allele[i]];
-  if (per_base) for (size_t i = 0; i < e->phys_pb.size(); ++i) per_base[i] = block[e->phys_pb[i]];
-  if (grouped) for (size_t i = 0; i < e->phys_grouped.size(); ++i) grouped[i] = block[e->phys_grouped[i]];
-  for (size_t i = 0; i + 3 < e->hit_fix.size(); i += 4) {  // a hit = one each of allele-sum, group {allele} and the base
-    const uint32_t hits = block[e->hit_fix[i]];
-    if (allele_sum) allele_sum[e->hit_fix[i + 1]] += hits;
-    if (grouped) grouped[e->hit_fix[i + 2]] += hits;
-    if (per_base) per_base[e->hit_fix[i + 3]] += hits;
+  if (!allele_sum && !per_base && !grouped) return GMX_OK;  // (a caller after the read counters alone: no block to copy)
+  std::vector<uint32_t> block(std::max<size_t>(e->n_acc * count, 1));
+  if (e->n_acc) HIP_TRY(hipMemcpy(block.data(), e->d_fused + first * e->n_acc, e->n_acc * count * 4, hipMemcpyDeviceToHost));
+  if (allele_sum) std::fill(allele_sum, allele_sum + e->phys_allele.size(), 0u);
+  if (per_base) std::fill(per_base, per_base + e->phys_pb.size(), 0u);
+  if (grouped) std::fill(grouped, grouped + e->phys_grouped.size(), 0u);
+  for (size_t k = 0; k < count; ++k) gather_block(e, block.data() + k * e->n_acc, allele_sum, per_base, grouped);
+  return GMX_OK;
+}
+
+int gmx_coverage_fetch(gmx_engine *e, uint32_t *allele_sum, uint32_t *per_base, uint32_t *grouped, gmx_stats *stats) try {
+  if (!e) {
+    gmx_set_error("null engine");
+    return GMX_EINVAL;
+  }
+  {  // (per strand: the totals are both blocks added)
+    int rc = fetch_blocks(e, 0, e->record_strands ? 2 : 1, allele_sum, per_base, grouped);
+    if (rc) return rc;
   }
   if (stats) {
     unsigned long long s[5];
@@ -2090,6 +2124,62 @@ int gmx_coverage_fetch(gmx_engine *e, uint32_t *allele_sum, uint32_t *per_base, 
   }
   return GMX_OK;
 } GMX_GUARD_INT("gmx_coverage_fetch")
+
+int gmx_coverage_fetch_strand(gmx_engine *e, int strand, uint32_t *allele_sum, uint32_t *per_base, uint32_t *grouped_dense) try {
+  if (!e) {
+    gmx_set_error("null engine");
+    return GMX_EINVAL;
+  }
+  if (!e->record_strands) {
+    gmx_set_error("gmx_coverage_fetch_strand: the engine does not record per strand (gmx_engine_record_strands)");
+    return GMX_EINVAL;
+  }
+  if (strand != 0 && strand != 1) {
+    gmx_set_error("gmx_coverage_fetch_strand: strand is 0 (forward) or 1 (reverse complement)");
+    return GMX_EINVAL;
+  }
+  return fetch_blocks(e, (size_t)strand, 1, allele_sum, per_base, grouped_dense);
+} GMX_GUARD_INT("gmx_coverage_fetch_strand")
+
+// The engine's one-block or two-block allocation. Nothing is recorded and nothing is in flight when this runs, so the new
+// block is simply a zeroed one; the old one stays untouched until the new one exists.
+static int set_record_strands(gmx_engine *e, bool on) {
+  if (e->record_strands == on) return GMX_OK;
+  const size_t n_fused = (on ? 2 : 1) * e->n_acc + 32;
+  if (n_fused + 32 > 0xFFFFFFFFull) {  // (the resets' word counts and CoverAcc::rev_off are 32 bits)
+    gmx_set_error("gmx_engine_record_strands: two accumulator blocks of this index exceed 2^32 words");
+    return GMX_EINVAL;
+  }
+  uint32_t *old = e->d_fused, *q = nullptr;
+  int rc = e->alloc(&q, n_fused + 32, true);  // + 16 words of read counters + log cursor
+  if (rc) return rc;
+  e->release(old);
+  e->record_strands = on;
+  e->reset_pending = false;  // (a queued reset: the fresh block is zero)
+  for (gmx_engine *w : {e, e->twin}) {  // the twin's alias of the block and every derived pointer follow
+    if (!w) continue;
+    w->d_fused = q;
+    w->n_fused = n_fused;
+    w->d_limbs = q + n_fused - 32;
+    w->d_stats = reinterpret_cast<unsigned long long *>(q + n_fused);
+    w->d_log_cursor = q + n_fused + 16;
+  }
+  return GMX_OK;
+}
+
+int gmx_engine_record_strands(gmx_engine *e, int on) try {
+  if (!e) {
+    gmx_set_error("null engine");
+    return GMX_EINVAL;
+  }
+  if (e->recorded) {
+    gmx_set_error("gmx_engine_record_strands: coverage has been recorded since the last reset (call gmx_engine_reset first)");
+    return GMX_EINVAL;
+  }
+  HIP_TRY(hipSetDevice(e->opts.device));
+  HIP_TRY(hipDeviceSynchronize());  // the engine's work (a reset still queued is dropped: the fresh block is zero)
+  return set_record_strands(e, on != 0);
+} GMX_GUARD_INT("gmx_engine_record_strands")
 
 int gmx_engine_record_outcomes(gmx_engine *e, int on) try {
   if (!e) {
@@ -2172,6 +2262,7 @@ void gmx_engine_raw(gmx_engine *e, GmxEngineRaw *out) {
   out->d_fused = e->d_fused;
   out->n_fused = e->n_fused;
   out->log_sites = e->log_sites;
+  out->record_strands = e->record_strands;
 }
 
 int gmx_engine_log_export(gmx_engine *e, std::vector<uint32_t> &out) {

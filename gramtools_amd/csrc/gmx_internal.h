@@ -35,9 +35,10 @@ uint64_t gmx_index_serial(const gmx_index *ix);  // unique within the process
 // What the multi-GPU exchange (gmx_multi.hip) needs of an engine (gmx_engine.hip).
 struct GmxEngineRaw {
   int device;
-  uint32_t *d_fused;  // the accumulator block + 32 counter-limb words (gmx_coverage_device)
+  uint32_t *d_fused;  // the accumulator block(s) + 32 counter-limb words (gmx_coverage_device)
   size_t n_fused;
   bool log_sites;     // the index has sites that use the grouped log
+  bool record_strands;  // two blocks (gmx_engine_record_strands): d_fused and n_fused change with it — take a fresh copy before an exchange
 };
 void gmx_engine_raw(gmx_engine *e, GmxEngineRaw *out);
 uint64_t gmx_engine_outcome_epoch(const gmx_engine *e);  // resets of the outcome buffer so far (gmx_group's ledger)

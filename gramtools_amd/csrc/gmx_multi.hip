@@ -547,7 +547,13 @@ int gmx_group_allreduce(gmx_group *g) try {
   for (auto &m : g->ms) {
     int rc = gmx_engine_sync(m.e);
     if (rc) return rc;
+    gmx_engine_raw(m.e, &m.raw);  // (gmx_engine_record_strands replaces the block)
   }
+  for (auto &m : g->ms)
+    if (m.raw.record_strands != g->ms[0].raw.record_strands || m.raw.n_fused != g->ms[0].raw.n_fused) {
+      gmx_set_error("gmx_group_allreduce: the members disagree on per-strand recording (gmx_group_record_strands sets all of them)");
+      return GMX_EINVAL;
+    }
   int rc = g->use_rccl ? gmx_exchange(g->ms, (int)g->ms.size()) : gmx_exchange_peer(g->ms);
   if (rc) return rc;
   for (auto &m : g->ms) {
@@ -556,6 +562,26 @@ int gmx_group_allreduce(gmx_group *g) try {
   }
   return GMX_OK;
 } GMX_GUARD_INT("gmx_group_allreduce")
+
+int gmx_group_record_strands(gmx_group *g, int on) try {
+  if (!g || g->ms.empty()) {
+    gmx_set_error("null group");
+    return GMX_EINVAL;
+  }
+  for (auto &m : g->ms) gmx_engine_raw(m.e, &m.raw);  // (what every member records now)
+  for (size_t i = 0; i < g->ms.size(); ++i) {
+    const int rc = gmx_engine_record_strands(g->ms[i].e, on);
+    if (rc) {  // all or none: the members before go back to what they recorded
+      for (size_t j = 0; j < i; ++j) {
+        (void)gmx_engine_record_strands(g->ms[j].e, g->ms[j].raw.record_strands ? 1 : 0);
+        gmx_engine_raw(g->ms[j].e, &g->ms[j].raw);
+      }
+      return rc;
+    }
+  }
+  for (auto &m : g->ms) gmx_engine_raw(m.e, &m.raw);
+  return GMX_OK;
+} GMX_GUARD_INT("gmx_group_record_strands")
 
 int gmx_comm_unique_id(uint8_t *out128) try {
   if (!rccl().ok) {
@@ -613,6 +639,7 @@ int gmx_comm_allreduce_coverage(gmx_comm *c, void *hip_stream) try {
   }
   HIP_TRY(hipSetDevice(c->m.raw.device));
   c->m.stream = (hipStream_t)hip_stream;
+  gmx_engine_raw(c->m.e, &c->m.raw);  // (gmx_engine_record_strands replaces the block; every rank must be in the same mode)
   std::vector<Member> ms(1, c->m);
   return gmx_exchange(ms, c->world);
 } GMX_GUARD_INT("gmx_comm_allreduce_coverage")

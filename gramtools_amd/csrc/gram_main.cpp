@@ -79,7 +79,14 @@ const char *kGenotypeHelp =
     "                              byte per read in the order of the reads files: bits 0-1 the read as given, bits 2-3 its\n"
     "                              reverse complement (0 skipped, 1 a k-mer not in the index, 2 no exact mapping, 3 exactly\n"
     "                              mapped), bits 4 / 5 that orientation had several mapping instances to draw from — and\n"
-    "                              read_outcomes.json, the count of every byte value\n";
+    "                              read_outcomes.json, the count of every byte value\n"
+    "  --strand_coverage           coverage per strand (engine extension): writes, beside the three coverage files,\n"
+    "                              coverage/allele_sum_coverage.forward and .reverse and\n"
+    "                              coverage/allele_base_coverage.forward.json and .reverse.json — what the reads as given and\n"
+    "                              what their reverse complements recorded, in the formats of allele_sum_coverage and\n"
+    "                              allele_base_coverage.json but as RAW totals (no 16-bit wrap, no saturation): entry by entry\n"
+    "                              forward + reverse = allele_sum_coverage (mod 65536) and min(forward + reverse, 65535) =\n"
+    "                              allele_base_coverage.json. Grouped allele counts are not split\n";
 
 [[noreturn]] void die(const std::string &msg, int code = 1) {
   std::cout << msg << std::endl;
@@ -2199,6 +2206,10 @@ int run_genotype(const Args &a) {
   std::vector<OutcomeSeg> outcome_segs;
   if (read_outcomes)
     for (int d = 0; d < gmx_group_size(grp); ++d) GMX_CHECK(gmx_engine_record_outcomes(gmx_group_engine(grp, d), 1));
+  // --strand_coverage: every engine keeps the reads' and their reverse complements' coverage apart, across samples (a reset
+  // zeroes both blocks); the exchange carries both
+  const bool strand_coverage = a.has("strand_coverage");
+  if (strand_coverage) GMX_CHECK(gmx_group_record_strands(grp, 1));
   auto note_outcomes = [&](int engine, uint64_t n) {  // BEFORE the call that hands n reads to `engine` (or to the group)
     if (!read_outcomes || n == 0) return;
     const int64_t at = engine < 0 ? gmx_group_outcome_count(grp) : gmx_engine_outcome_count(gmx_group_engine(grp, engine));
@@ -2415,6 +2426,14 @@ int run_genotype(const Args &a) {
   std::vector<uint32_t> glog(std::max<int64_t>(n_log, 1));
   if (n_log) gmx_coverage_fetch_grouped_log(eng, glog.data(), (uint64_t)n_log);
 
+  std::vector<uint32_t> strand_allele_sum[2], strand_per_base[2];  // --strand_coverage: raw totals per strand
+  if (strand_coverage)
+    for (int sd = 0; sd < 2; ++sd) {
+      strand_allele_sum[sd].assign(allele_sum.size(), 0);
+      strand_per_base[sd].assign(per_base.size(), 0);
+      GMX_CHECK(gmx_coverage_fetch_strand(eng, sd, strand_allele_sum[sd].data(), strand_per_base[sd].data(), nullptr));
+    }
+
   gmx_depth_stats ds;  // readstats.compute_coverage_depth, quasimap.cpp:48
   GMX_CHECK(gmx_compute_coverage_depth(ix, per_base.data(), grouped.data(), glog.data(), (uint64_t)n_log, &ds));
   rs.mean_cov_depth = ds.mean_cov_depth;
@@ -2468,20 +2487,20 @@ int run_genotype(const Args &a) {
   }
   std::string rs_path = join(run_dir, "read_stats.json");
   std::cout << "Writing read stats to " << rs_path << std::endl;
-  std::thread cov_writer([&]() {
-  {  // coverage::dump::allele_sum (allele_sum.cpp:45-57): uint16 wrap
-    std::ofstream o(join(cov_dir, "allele_sum_coverage"));
+  // (u16: the reference's file semantics; the per-strand files of --strand_coverage hold the raw totals)
+  auto write_allele_sum = [&](const std::string &path, const std::vector<uint32_t> &allele_sum, bool u16) {
+    std::ofstream o(path);
     for (uint32_t s = 0; s < info.n_sites; ++s) {
       for (uint32_t al = 0; al < n_alleles[s]; ++al) {
-        o << (allele_sum[as_off[s] + al] & 0xFFFFu);
+        o << (allele_sum[as_off[s] + al] & (u16 ? 0xFFFFu : 0xFFFFFFFFu));
         if (al + 1 < n_alleles[s]) o << " ";
       }
       o << "\n";
     }
-    close_checked(o, join(cov_dir, "allele_sum_coverage"));
-  }
-  {  // coverage::dump::allele_base (allele_base.cpp:49-107): saturating uint16; [] for nested PRGs
-    std::ofstream o(join(cov_dir, "allele_base_coverage.json"));
+    close_checked(o, path);
+  };
+  auto write_allele_base = [&](const std::string &path, const std::vector<uint32_t> &per_base, bool u16) {
+    std::ofstream o(path);
     o << "{\"allele_base_counts\":[";
     if (!info.is_nested) {
       std::vector<uint32_t> pb_off(std::max<uint32_t>(info.n_allele_slots, 1)), pb_len(std::max<uint32_t>(info.n_allele_slots, 1));
@@ -2492,7 +2511,7 @@ int run_genotype(const Args &a) {
           o << "[";
           uint32_t slot = as_off[s] + al;
           for (uint32_t i = 0; i < pb_len[slot]; ++i) {
-            o << std::min<uint32_t>(per_base[pb_off[slot] + i], 65535u);
+            o << std::min<uint32_t>(per_base[pb_off[slot] + i], u16 ? 65535u : 0xFFFFFFFFu);
             if (i + 1 < pb_len[slot]) o << ",";
           }
           o << "]";
@@ -2503,8 +2522,17 @@ int run_genotype(const Args &a) {
       }
     }
     o << "]}\n";
-    close_checked(o, join(cov_dir, "allele_base_coverage.json"));
-  }
+    close_checked(o, path);
+  };
+  std::thread cov_writer([&]() {
+  write_allele_sum(join(cov_dir, "allele_sum_coverage"), allele_sum, true);  // coverage::dump::allele_sum (allele_sum.cpp:45-57): uint16 wrap
+  write_allele_base(join(cov_dir, "allele_base_coverage.json"), per_base, true);  // coverage::dump::allele_base (allele_base.cpp:49-107): saturating uint16; [] for nested PRGs
+  if (strand_coverage)
+    for (int sd = 0; sd < 2; ++sd) {
+      const std::string name = sd ? "reverse" : "forward";
+      write_allele_sum(join(cov_dir, "allele_sum_coverage." + name), strand_allele_sum[sd], false);
+      write_allele_base(join(cov_dir, "allele_base_coverage." + name + ".json"), strand_per_base[sd], false);
+    }
   {  // coverage::dump::grouped_allele_counts (grouped_allele_counts.cpp:51-110): uint16 wrap, arbitrary group ids
     std::vector<std::map<std::vector<int32_t>, uint32_t>> sites(info.n_sites);
     for (uint32_t s = 0; s < info.n_sites; ++s) {

@@ -91,7 +91,9 @@ class _DevArray:
 
 
 def fused_coverage_tensor(qm):
-    """One int32 tensor aliasing the engine's whole coverage block (allele_sum | per_base | grouped | counter limbs)."""
+    """One int32 tensor aliasing the engine's whole coverage block (allele_sum | per_base | grouped | counter limbs; with
+    Quasimapper.record_strands both strands' blocks, then the limbs — every rank must be in the same mode). record_strands
+    replaces the block: a tensor taken before it is stale, and allreduce_device_coverage refuses it."""
     import torch
     dc = qm.device_coverage()
     return torch.as_tensor(_DevArray(dc.fused, dc.n_fused, "<i4"), device="cuda")
@@ -104,6 +106,11 @@ def allreduce_device_coverage(qm, dist, tensor=None, stream=None):
     (site, allele set), small), after which every rank's engine holds the sum of all logs.
     :class:`CoverageComm` does the same inside the library (the implementation `gram --devices` uses)."""
     t = fused_coverage_tensor(qm) if tensor is None else tensor
+    if tensor is not None:  # (Quasimapper.record_strands replaces the block: a tensor from before aliases freed memory)
+        dc = qm.device_coverage()
+        if t.data_ptr() != int(dc.fused) or t.numel() != int(dc.n_fused):
+            raise ValueError("allreduce_device_coverage: the tensor does not alias the engine's coverage block (taken before "
+                             "record_strands?): take a fresh fused_coverage_tensor(qm)")
     qm.reduce_begin(stream)
     dist.all_reduce(t)
     qm.reduce_end(stream)

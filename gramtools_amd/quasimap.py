@@ -563,6 +563,11 @@ class Quasimapper:
         check(self.lib.gmx_engine_fetch_outcomes(self.h, first, n, _p(out, C.c_uint8)))
         return out[:n]
 
+    def record_strands(self, on: bool = True):
+        """Coverage per strand (gmx_engine_record_strands): what the reads as given recorded and what their reverse complements
+        recorded are kept apart; see coverage(strand=...). Only while nothing is recorded: after creation or reset()."""
+        check(self.lib.gmx_engine_record_strands(self.h, 1 if on else 0))
+
     def enable_timing(self, on=True):
         check(self.lib.gmx_engine_enable_timing(self.h, 1 if on else 0))
 
@@ -673,12 +678,24 @@ class Quasimapper:
             check(self.lib.gmx_coverage_fetch_grouped_log(self.h, _p(log, C.c_uint32), n))
         return log[:n]
 
-    def coverage(self) -> Coverage:
+    def coverage(self, strand=None) -> Coverage:
+        """The totals, or with ``strand`` 0 (forward) / 1 (reverse complement) one strand's share of them (record_strands;
+        gmx_coverage_fetch_strand). A strand's Coverage carries an empty grouped log — the log is not split — and the read
+        counters of the whole run."""
         info = self.index.info
         a = np.zeros(max(info.n_allele_slots, 1), dtype=np.uint32)
         p = np.zeros(max(info.n_per_base_slots, 1), dtype=np.uint32)
         g = np.zeros(max(info.n_grouped_slots, 1), dtype=np.uint32)
         st = _lib.Stats()
+        if strand is not None:
+            if strand not in (0, 1):
+                raise ValueError("strand is None (totals), 0 (forward) or 1 (reverse complement)")
+            check(self.lib.gmx_coverage_fetch_strand(self.h, int(strand), _p(a, C.c_uint32), _p(p, C.c_uint32), _p(g, C.c_uint32)))
+            check(self.lib.gmx_coverage_fetch(self.h, None, None, None, C.byref(st)))
+            stats = QuasimapReadsStats(st.all_reads_count, st.skipped_reads_count, st.missing_kmer_reads_count,
+                                       st.no_extension_reads_count, st.exact_mapped_reads_count)
+            return Coverage(self.index, a[:info.n_allele_slots], p[:info.n_per_base_slots], g[:info.n_grouped_slots],
+                            np.zeros(0, dtype=np.uint32), stats)
         check(self.lib.gmx_coverage_fetch(self.h, _p(a, C.c_uint32), _p(p, C.c_uint32), _p(g, C.c_uint32), C.byref(st)))
         n = check(self.lib.gmx_coverage_fetch_grouped_log(self.h, None, 0))
         log = np.zeros(max(n, 1), dtype=np.uint32)
@@ -905,6 +922,10 @@ class QuasimapperGroup:
         for i in range(self.lib.gmx_group_size(self.h)):
             check(self.lib.gmx_engine_record_outcomes(C.c_void_p(self.lib.gmx_group_engine(self.h, i)), 1 if on else 0))
 
+    def record_strands(self, on: bool = True):
+        """Coverage per strand on every member (gmx_group_record_strands; Quasimapper.record_strands)."""
+        check(self.lib.gmx_group_record_strands(self.h, 1 if on else 0))
+
     def outcome_count(self) -> int:
         return check(self.lib.gmx_group_outcome_count(self.h))
 
@@ -919,12 +940,13 @@ class QuasimapperGroup:
         check(self.lib.gmx_group_fetch_outcomes(self.h, first, n, _p(out, C.c_uint8)))
         return out[:n]
 
-    def coverage(self, member: int = 0) -> Coverage:
-        """Coverage held by engine `member` (after :meth:`allreduce`: the totals of the whole job, on every member)."""
+    def coverage(self, member: int = 0, strand=None) -> Coverage:
+        """Coverage held by engine `member` (after :meth:`allreduce`: the totals of the whole job, on every member); with
+        ``strand`` 0 / 1 one strand's share (record_strands)."""
         view = Quasimapper.__new__(Quasimapper)
         view.lib, view.index, view.h = self.lib, self.index, C.c_void_p(self.lib.gmx_group_engine(self.h, member))
         try:
-            return view.coverage()
+            return view.coverage(strand)
         finally:
             view.h = None  # the group owns the engine
 

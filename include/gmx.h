@@ -522,6 +522,25 @@ int gmx_coverage_fetch(gmx_engine *e, uint32_t *allele_sum, uint32_t *per_base, 
 int gmx_engine_record_outcomes(gmx_engine *e, int on);
 int64_t gmx_engine_outcome_count(gmx_engine *e);
 int gmx_engine_fetch_outcomes(gmx_engine *e, uint64_t first, uint64_t n, uint8_t *out);
+/* Coverage per strand (off by default; nothing changes while it is off). Every read is mapped as given and reverse-complemented;
+ * with recording on, the engine keeps TWO accumulator blocks — what the reads as given added, and what their reverse complements
+ * added — instead of one: allele-sum, dense grouped counts and per-base counts of every site, each per strand. The read counters
+ * are not split. The grouped log (sites with more than 8 alleles, gmx_coverage_fetch_grouped_log) is NOT split either: such a
+ * site's allele-sum and per-base counts are per strand, its grouped counts are totals only. With gmx_engine_opts::forward_only
+ * the reverse block stays zero.
+ *   gmx_engine_record_strands  may only be called while nothing is recorded — after gmx_engine_create, gmx_engine_reset or a
+ *     gmx_engine_reset_async (it waits for the engine's work) — and returns GMX_EINVAL otherwise. It gives the engine its one-block
+ *     or two-block allocation; when that fails it returns the error's code, the mode and the old block unchanged.
+ *   gmx_coverage_fetch_strand  strand 0: forward, 1: reverse complement. The raw uint32 totals of that block, gathered as
+ *     gmx_coverage_fetch gathers (any pointer may be NULL). GMX_EINVAL while recording is off.
+ *   gmx_coverage_fetch         with recording on: both blocks added (uint32 wrap) — identical to an engine with recording off.
+ *   gmx_coverage_device        with recording on `fused` is [forward block | reverse block | 32 limb words], n_fused = 2 * block
+ *     + 32: the exchange carries both strands. Every engine that takes part in one exchange must be in the same mode:
+ *     gmx_group_record_strands sets all members of a group (gmx_group_allreduce returns GMX_EINVAL when they disagree); under
+ *     gmx_comm_* every rank calls gmx_engine_record_strands with the same value before it maps (the all-reduce's word counts
+ *     must agree, and nothing can check that across processes). */
+int gmx_engine_record_strands(gmx_engine *e, int on);
+int gmx_coverage_fetch_strand(gmx_engine *e, int strand, uint32_t *allele_sum, uint32_t *per_base, uint32_t *grouped_dense);
 /* Grouped counts of sites with more than 8 alleles (grouped_allele_counts.cpp:17-49 for sites without dense slots).
  * Returns the number of uint32 words of the log (and copies it when it fits cap_words). The log is a sequence of records
  *   [site_index, n_ids, ids...]                                     worth +1, or
@@ -618,6 +637,10 @@ int gmx_group_allreduce(gmx_group *g); /* the exchange; synchronises every engin
  * gmx_group_map_reads_* since the members' last reset. The exchange is not involved. */
 int64_t gmx_group_outcome_count(gmx_group *g);
 int gmx_group_fetch_outcomes(gmx_group *g, uint64_t first, uint64_t n, uint8_t *out);
+/* Coverage per strand on every member (gmx_engine_record_strands; the same rule: while no member has recorded anything). All
+ * members or none: when one cannot be switched, those before it go back. After gmx_group_allreduce every member's two blocks
+ * hold the whole job's per-strand totals. */
+int gmx_group_record_strands(gmx_group *g, int on);
 
 typedef struct gmx_comm gmx_comm; /* one engine per PROCESS (torch.distributed.run, mpirun, ...): rank 0 makes the id,
                                      the launcher's own channel broadcasts its 128 bytes, every rank creates its comm */
