@@ -163,6 +163,8 @@ SYMBOLS = {
     "gmx_engine_fetch_outcomes": (C.c_int, [_vp, _u64, _u64, _u8p]),
     "gmx_engine_record_strands": (C.c_int, [_vp, C.c_int]),
     "gmx_coverage_fetch_strand": (C.c_int, [_vp, C.c_int, _u32p, _u32p, _u32p]),
+    "gmx_coverage_fetch_grouped_log_strand": (_i64, [_vp, C.c_int, _u32p, _u64]),
+    "gmx_coverage_export_grouped_log": (_i64, [_vp, _u32p, _u64]),
     "gmx_coverage_import_grouped_log": (C.c_int, [_vp, _u32p, _u64, C.c_int]),
     "gmx_grouped_log_merge_gathered": (_i64, [_vp, _vp, C.c_int, _u64, _vp, _u64]),
     "gmx_finalize_u16": (None, [_u32p, _u64, C.c_int]),
@@ -173,6 +175,8 @@ SYMBOLS = {
     "gmx_infer_write_fasta": (C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_char_p]),
     "gmx_infer_debug_text": (_i64, [_vp, C.c_char_p, _u64]),
     "gmx_infer_site_json": (_i64, [_vp, _u32, C.c_char_p, _u64]),
+    "gmx_infer_annotate_strands": (C.c_int, [_vp, _u32p, _u32p, _u32p, _u64, _u32p, _u64]),
+    "gmx_strand_bias_phred": (C.c_double, [_u64, _u64, _u64, _u64]),
     "gmx_infer_model": (_i64, [_u32, C.POINTER(C.c_char_p), _u32p, _u32p, _i32p, _u8p, _u32, _u32p, _i32p, _u32p, C.c_int,
                                C.c_double, C.c_double, C.c_double, C.c_char_p, _u64]),
     "gmx_infer_debug": (_i64, [C.c_int, _u32, C.POINTER(C.c_char_p), _u32p, _u32p, _i32p, _u8p, _u32, _u32p, _i32p, _u32p, C.c_int,

@@ -1,6 +1,7 @@
 // gmx_capi.cpp — host half of the C ABI: index construction, introspection, seeds, u16 finalisation.
 #include <atomic>
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -698,14 +699,15 @@ int gmx_pack_reads_2bit(const uint8_t *reads, const uint64_t *offsets, uint32_t 
 
 // ---- grouped logs as values: what every rank does with the all-gathered logs of an exchange (gmx_multi.hip) -----------
 // `gathered` holds `world` slices of `pad` words, slice r carrying sizes[r] words of rank r's log (either record form,
-// GMX_LOG_PAD words skipped); the result is one counted record per distinct (site, ids), in key order.
+// GMX_LOG_PAD words skipped, GMX_LOG_REVERSE kept); the result is one counted record per distinct (site, ids) and strand, in
+// key order, a key's forward record before its reverse one (which carries GMX_LOG_REVERSE again).
 int64_t gmx_grouped_log_merge_gathered(const uint32_t *gathered, const uint64_t *sizes, int world, uint64_t pad, uint32_t *out,
                                        uint64_t cap_words) try {
   if ((!gathered && pad) || !sizes || world < 0) {
     gmx_set_error("gmx_grouped_log_merge_gathered: null argument");
     return GMX_EINVAL;
   }
-  std::map<std::vector<uint32_t>, uint64_t> counts;
+  std::map<std::vector<uint32_t>, std::array<uint64_t, 2>> counts;
   std::vector<uint32_t> key;
   for (int r = 0; r < world; ++r) {
     if (sizes[r] > pad) {
@@ -723,7 +725,7 @@ int64_t gmx_grouped_log_merge_gathered(const uint32_t *gathered, const uint64_t 
         gmx_set_error("corrupt grouped log");
         return GMX_EINVAL;
       }
-      const uint32_t n_ids = w[i + 1] & ~GMX_LOG_COUNTED;
+      const uint32_t n_ids = w[i + 1] & ~(GMX_LOG_COUNTED | GMX_LOG_REVERSE);
       const uint64_t head = (w[i + 1] & GMX_LOG_COUNTED) ? 4 : 2;
       if (i + head + n_ids > n) {
         gmx_set_error("corrupt grouped log");
@@ -732,21 +734,27 @@ int64_t gmx_grouped_log_merge_gathered(const uint32_t *gathered, const uint64_t 
       const uint64_t count = head == 4 ? ((uint64_t)w[i + 2] | ((uint64_t)w[i + 3] << 32)) : 1;
       key.assign(1, w[i]);
       key.insert(key.end(), w + i + head, w + i + head + n_ids);
-      counts[key] += count;
+      auto it = counts.find(key);  // (a record is never worth zero: a strand that was seen has a non-zero count)
+      if (it == counts.end()) it = counts.emplace(key, std::array<uint64_t, 2>{0, 0}).first;
+      it->second[(w[i + 1] & GMX_LOG_REVERSE) ? 1 : 0] += count;
       i += head + n_ids;
     }
   }
   uint64_t at = 0;
   for (auto const &kv : counts) {
     const uint64_t words = 4 + (kv.first.size() - 1);
-    if (out && at + words <= cap_words) {
-      out[at] = kv.first[0];
-      out[at + 1] = (uint32_t)(kv.first.size() - 1) | GMX_LOG_COUNTED;
-      out[at + 2] = (uint32_t)kv.second;
-      out[at + 3] = (uint32_t)(kv.second >> 32);
-      for (size_t j = 1; j < kv.first.size(); ++j) out[at + 3 + j] = kv.first[j];
+    for (int s = 0; s < 2; ++s) {
+      if (s == 1 && !kv.second[1]) continue;                  // no reverse record seen
+      if (s == 0 && !kv.second[0] && kv.second[1]) continue;  // reverse records only
+      if (out && at + words <= cap_words) {
+        out[at] = kv.first[0];
+        out[at + 1] = (uint32_t)(kv.first.size() - 1) | GMX_LOG_COUNTED | (s ? GMX_LOG_REVERSE : 0u);
+        out[at + 2] = (uint32_t)kv.second[s];
+        out[at + 3] = (uint32_t)(kv.second[s] >> 32);
+        for (size_t j = 1; j < kv.first.size(); ++j) out[at + 3 + j] = kv.first[j];
+      }
+      at += words;
     }
-    at += words;
   }
   return (int64_t)at;
 } GMX_GUARD_INT("gmx_grouped_log_merge_gathered")

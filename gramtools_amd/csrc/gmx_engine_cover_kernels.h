@@ -107,7 +107,7 @@ struct CoverLogPart {
   }
   __device__ __forceinline__ bool log_grouped_begin(uint32_t site_index, uint32_t n_ids) {
     log[log_at++] = site_index;
-    log[log_at++] = n_ids;
+    log[log_at++] = n_ids | (acc_off ? GMX_LOG_REVERSE : 0u);  // the task's strand: acc_off is non-zero only for a reverse-complement task of an engine that records strands
     return true;
   }
   __device__ __forceinline__ void log_grouped_id(int32_t a) { log[log_at++] = (uint32_t)a; }

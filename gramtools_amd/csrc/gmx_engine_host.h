@@ -70,7 +70,9 @@ struct gmx_engine {
   uint64_t heap_words = 0;
   bool log_sites = false;          // the index has sites with more than 8 alleles
   // grouped log: drained into `log_counts` (records with counts) whenever the device log may run full, and at fetch time
-  std::map<std::vector<uint32_t>, uint64_t> log_counts;  // key = [site_index, ids...]
+  // key = [site_index, ids...]; value = the records of forward and of reverse-complement tasks (GMX_LOG_REVERSE: the second
+  // is zero unless the engine records strands)
+  std::map<std::vector<uint32_t>, std::array<uint64_t, 2>> log_counts;
   // Exact accounting (round 3): after every batch of an engine whose index uses the log, the log cursor and the lengths
   // of the three retry lists are copied to page-locked words; before the next batch (and before any reader of the
   // coverage) log_settle() looks at them: entries that found the log full are redone after a drain (launch_log_replay),
@@ -293,8 +295,8 @@ static int flush_reset(gmx_engine *e) {
 }
 
 // Grouped log -> host. Waits for the device, adds the log's records to e->log_counts when more than `keep_below` words are in
-// use (and empties the device log), and notes how full it is. Records: [site_index, n_ids, ids...], each worth +1;
-// GMX_LOG_PAD words are padding (CoverLogPart::log_reserve).
+// use (and empties the device log), and notes how full it is. Records: [site_index, n_ids | strand bit, ids...], each
+// worth +1 on its strand (GMX_LOG_REVERSE); GMX_LOG_PAD words are padding (CoverLogPart::log_reserve).
 static int log_settle(gmx_engine *e);
 static int gmx_log_drain(gmx_engine *e, uint64_t keep_below) {
   int frc = flush_reset(e);
@@ -314,14 +316,19 @@ static int gmx_log_drain(gmx_engine *e, uint64_t keep_below) {
       ++i;
       continue;
     }
-    if (i + 2 > w.size() || i + 2 + (size_t)w[i + 1] > w.size()) {  // reservations are exact (log_reserve): never expected
+    const size_t n_ids = i + 2 > w.size() ? 0 : (size_t)(w[i + 1] & ~GMX_LOG_REVERSE);
+    if (i + 2 > w.size() || i + 2 + n_ids > w.size()) {  // reservations are exact (log_reserve): never expected
       gmx_set_error("grouped-allele-count log: malformed record at word " + std::to_string(i) + " of " + std::to_string(w.size()));
       return GMX_EREF;
     }
+    if ((w[i + 1] & GMX_LOG_REVERSE) && !(e->owner ? e->owner : e)->record_strands) {  // only CoverAcc::rev_off != 0 sets the bit: never expected
+      gmx_set_error("grouped-allele-count log: a reverse-complement record at word " + std::to_string(i) + " of an engine that does not record per strand");
+      return GMX_EREF;
+    }
     key.assign(1, w[i]);
-    key.insert(key.end(), w.begin() + i + 2, w.begin() + i + 2 + w[i + 1]);
-    e->log_counts[key] += 1;
-    i += 2 + w[i + 1];
+    key.insert(key.end(), w.begin() + i + 2, w.begin() + i + 2 + n_ids);
+    e->log_counts[key][(w[i + 1] & GMX_LOG_REVERSE) ? 1 : 0] += 1;
+    i += 2 + n_ids;
   }
   HIP_TRY(hipMemset(e->d_log_cursor, 0, 4));
   e->log_known = 0;
@@ -2219,25 +2226,68 @@ int gmx_engine_fetch_outcomes(gmx_engine *e, uint64_t first, uint64_t n, uint8_t
   return GMX_OK;
 } GMX_GUARD_INT("gmx_engine_fetch_outcomes")
 
+// Counted records of e->log_counts into `out` (as far as they fit) and their length in words: one strand's counts, their sums,
+// or the exchange form (up to two records per key, the reverse one with GMX_LOG_REVERSE).
+enum LogForm { LOG_FORWARD = 0, LOG_REVERSE_ONLY = 1, LOG_TOTALS = 2, LOG_EXCHANGE = 3 };
+// what engines pass to each other: without strands every count is a forward one, the records of the totals
+static LogForm exchange_form(const gmx_engine *e) { return e->record_strands ? LOG_EXCHANGE : LOG_TOTALS; }
+static uint64_t emit_log_counts(const gmx_engine *e, LogForm which, uint32_t *out, uint64_t cap_words) {
+  uint64_t n = 0;
+  for (auto const &kv : e->log_counts) {  // [site_index, n_ids | GMX_LOG_COUNTED, count lo, count hi, ids...]
+    const uint64_t words = 4 + (kv.first.size() - 1);
+    for (int s = 0; s < (which == LOG_EXCHANGE ? 2 : 1); ++s) {
+      const uint64_t count = which == LOG_TOTALS ? kv.second[0] + kv.second[1] : kv.second[which == LOG_EXCHANGE ? s : which];
+      if (!count) continue;
+      if (out && n + words <= cap_words) {
+        out[n] = kv.first[0];
+        out[n + 1] = (uint32_t)(kv.first.size() - 1) | GMX_LOG_COUNTED | (which == LOG_EXCHANGE && s ? GMX_LOG_REVERSE : 0u);
+        out[n + 2] = (uint32_t)count;
+        out[n + 3] = (uint32_t)(count >> 32);
+        for (size_t j = 1; j < kv.first.size(); ++j) out[n + 3 + j] = kv.first[j];
+      }
+      n += words;
+    }
+  }
+  return n;
+}
+
 int64_t gmx_coverage_fetch_grouped_log(gmx_engine *e, uint32_t *out, uint64_t cap_words) try {
   if (!e) return GMX_EINVAL;
   if (hipSetDevice(e->opts.device) != hipSuccess) return GMX_EHIP;
   if (log_settle(e)) return GMX_EHIP;
   if (gmx_log_drain(e, 0)) return GMX_EHIP;
-  uint64_t n = 0;
-  for (auto const &kv : e->log_counts) {  // [site_index, n_ids | GMX_LOG_COUNTED, count lo, count hi, ids...]
-    const uint64_t words = 4 + (kv.first.size() - 1);
-    if (out && n + words <= cap_words) {
-      out[n] = kv.first[0];
-      out[n + 1] = (uint32_t)(kv.first.size() - 1) | GMX_LOG_COUNTED;
-      out[n + 2] = (uint32_t)kv.second;
-      out[n + 3] = (uint32_t)(kv.second >> 32);
-      for (size_t j = 1; j < kv.first.size(); ++j) out[n + 3 + j] = kv.first[j];
-    }
-    n += words;
-  }
-  return (int64_t)n;
+  return (int64_t)emit_log_counts(e, LOG_TOTALS, out, cap_words);
 } GMX_GUARD_INT("gmx_coverage_fetch_grouped_log")
+
+int64_t gmx_coverage_fetch_grouped_log_strand(gmx_engine *e, int strand, uint32_t *out, uint64_t cap_words) try {
+  if (!e) {
+    gmx_set_error("null engine");
+    return GMX_EINVAL;
+  }
+  if (!e->record_strands) {
+    gmx_set_error("gmx_coverage_fetch_grouped_log_strand: the engine does not record per strand (gmx_engine_record_strands)");
+    return GMX_EINVAL;
+  }
+  if (strand != 0 && strand != 1) {
+    gmx_set_error("gmx_coverage_fetch_grouped_log_strand: strand is 0 (forward) or 1 (reverse complement)");
+    return GMX_EINVAL;
+  }
+  if (hipSetDevice(e->opts.device) != hipSuccess) return GMX_EHIP;
+  if (log_settle(e)) return GMX_EHIP;
+  if (gmx_log_drain(e, 0)) return GMX_EHIP;
+  return (int64_t)emit_log_counts(e, strand ? LOG_REVERSE_ONLY : LOG_FORWARD, out, cap_words);
+} GMX_GUARD_INT("gmx_coverage_fetch_grouped_log_strand")
+
+int64_t gmx_coverage_export_grouped_log(gmx_engine *e, uint32_t *out, uint64_t cap_words) try {
+  if (!e) {
+    gmx_set_error("null engine");
+    return GMX_EINVAL;
+  }
+  if (hipSetDevice(e->opts.device) != hipSuccess) return GMX_EHIP;
+  if (log_settle(e)) return GMX_EHIP;
+  if (gmx_log_drain(e, 0)) return GMX_EHIP;
+  return (int64_t)emit_log_counts(e, exchange_form(e), out, cap_words);
+} GMX_GUARD_INT("gmx_coverage_export_grouped_log")
 
 int gmx_coverage_import_grouped_log(gmx_engine *e, const uint32_t *records, uint64_t n_words, int replace) try {
   if (!e || (!records && n_words)) {
@@ -2271,10 +2321,14 @@ int gmx_engine_log_export(gmx_engine *e, std::vector<uint32_t> &out) {
     if (frc) return frc;
     if ((frc = log_settle(e))) return frc;
   }
-  const int64_t n = gmx_coverage_fetch_grouped_log(e, nullptr, 0);
-  if (n < 0) return (int)n;
-  out.assign((size_t)n, 0);
-  if (n && gmx_coverage_fetch_grouped_log(e, out.data(), (uint64_t)n) < 0) return GMX_EHIP;
+  HIP_TRY(hipSetDevice(e->opts.device));
+  {
+    int rc = gmx_log_drain(e, 0);
+    if (rc) return rc;
+  }
+  const LogForm which = exchange_form(e);
+  out.assign((size_t)emit_log_counts(e, which, nullptr, 0), 0);
+  emit_log_counts(e, which, out.data(), out.size());
   return GMX_OK;
 }
 
@@ -2282,6 +2336,25 @@ int gmx_engine_log_import(gmx_engine *e, const uint32_t *w, size_t n_words, bool
   {
     int frc = flush_reset(e);
     if (frc) return frc;
+  }
+  const uint32_t flags = GMX_LOG_COUNTED | GMX_LOG_REVERSE;
+  for (size_t i = 0; i < n_words;) {  // all of it is checked before any of it counts
+    if (w[i] == GMX_LOG_PAD) {
+      ++i;
+      continue;
+    }
+    if (i + 2 > n_words) break;
+    const uint32_t n = w[i + 1] & ~flags;
+    const size_t head = (w[i + 1] & GMX_LOG_COUNTED) ? 4 : 2;
+    if (i + head + n > n_words) {
+      gmx_set_error("corrupt grouped log");
+      return GMX_EINVAL;
+    }
+    if ((w[i + 1] & GMX_LOG_REVERSE) && !e->record_strands) {
+      gmx_set_error("grouped log: a reverse-complement record (GMX_LOG_REVERSE) for an engine that does not record per strand");
+      return GMX_EINVAL;
+    }
+    i += head + n;
   }
   if (replace) {
     int rc = gmx_log_drain(e, 0);  // whatever is still on the device belongs to the totals being replaced
@@ -2295,16 +2368,12 @@ int gmx_engine_log_import(gmx_engine *e, const uint32_t *w, size_t n_words, bool
       continue;
     }
     if (i + 2 > n_words) break;
-    const uint32_t n = w[i + 1] & ~GMX_LOG_COUNTED;
+    const uint32_t n = w[i + 1] & ~flags;
     const size_t head = (w[i + 1] & GMX_LOG_COUNTED) ? 4 : 2;
-    if (i + head + n > n_words) {
-      gmx_set_error("corrupt grouped log");
-      return GMX_EINVAL;
-    }
     const uint64_t count = head == 4 ? ((uint64_t)w[i + 2] | ((uint64_t)w[i + 3] << 32)) : 1;
     key.assign(1, w[i]);
     key.insert(key.end(), w + i + head, w + i + head + n);
-    e->log_counts[key] += count;
+    e->log_counts[key][(w[i + 1] & GMX_LOG_REVERSE) ? 1 : 0] += count;
     i += head + n;
   }
   return GMX_OK;

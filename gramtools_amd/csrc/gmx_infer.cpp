@@ -119,6 +119,11 @@ struct Site {  // GenotypedSite + LevelGenotypedSite (interfaces.hpp:49-132, lev
   std::optional<Alleles> extra;
   double gt_conf = 0., gt_conf_percentile = 0.;
   std::string debug_info;  // --debug: next best genotype's sequences and coverages (model.cpp:452-465)
+  // gmx_infer_annotate_strands: per output allele, the grouped counts of the groups with its haplogroup, per strand (raw
+  // 64-bit sums), and the strand-bias score of the call; a null site keeps the flag and has no values
+  bool has_strands = false;
+  std::vector<uint64_t> cov_fwd, cov_rev;
+  double sb = 0.;
   bool is_null() const { return !genotype.empty() && genotype[0] == -1; }
   void make_null() {
     genotype = Gt{-1};
@@ -805,7 +810,15 @@ std::string site_json(const Site &s, const std::string *seg, size_t pos1) {  // 
   for (size_t i = 0; i < s.alleles.size(); ++i) o << (i ? "," : "") << jstr(s.alleles[i].seq);
   o << "],\"COV\":[[";
   for (size_t i = 0; i < s.covs.size(); ++i) o << (i ? "," : "") << jdouble(s.covs[i]);
-  o << "]],\"DP\":[" << s.total_cov << "],\"FT\":[[";
+  o << "]]";
+  if (s.has_strands) {
+    o << ",\"COV_FWD\":[[";
+    for (size_t i = 0; i < s.cov_fwd.size(); ++i) o << (i ? "," : "") << s.cov_fwd[i];
+    o << "]],\"COV_REV\":[[";
+    for (size_t i = 0; i < s.cov_rev.size(); ++i) o << (i ? "," : "") << s.cov_rev[i];
+    o << "]]";
+  }
+  o << ",\"DP\":[" << s.total_cov << "],\"FT\":[[";
   for (size_t i = 0; i < s.filters.size(); ++i) o << (i ? "," : "") << jstr(s.filters[i]);
   o << "]],\"GT\":[[";
   if (s.is_null())
@@ -814,7 +827,14 @@ std::string site_json(const Site &s, const std::string *seg, size_t pos1) {  // 
     for (size_t i = 0; i < s.genotype.size(); ++i) o << (i ? "," : "") << s.genotype[i];
   o << "]],\"GT_CONF\":[" << jdouble(s.gt_conf) << "],\"GT_CONF_PERCENTILE\":[" << jdouble(s.gt_conf_percentile) << "],\"HAPG\":[[";
   for (size_t i = 0; i < s.haplogroups.size(); ++i) o << (i ? "," : "") << s.haplogroups[i];
-  o << "]],\"POS\":" << pos1 << ",\"SEG\":" << jstr(seg ? *seg : std::string("")) << "}";
+  o << "]],\"POS\":" << pos1;
+  if (s.has_strands) {
+    if (s.is_null())
+      o << ",\"SB\":[null]";
+    else
+      o << ",\"SB\":[" << jdouble(s.sb) << "]";
+  }
+  o << ",\"SEG\":" << jstr(seg ? *seg : std::string("")) << "}";
   return o.str();
 }
 
@@ -896,16 +916,59 @@ std::string fmt_g(double v) {  // htslib writes FORMAT floats with %g of the flo
   return b;
 }
 
+const char *kCovFwdDesc = "Read coverage on each allele, reads mapped as given";
+const char *kCovRevDesc = "Read coverage on each allele, reads mapped as their reverse complement";
+const char *kSbDesc = "Phred-scaled two-sided Fisher exact probability of strand bias: called versus other haplogroups, by strand";
+
+// log of the hypergeometric probability of the table with x in its first cell, rows r1 / r2, first column c1
+struct Hypergeom {
+  uint64_t r1, r2, c1;
+  double base;
+  static double lg(uint64_t v) {
+    int sg = 0;
+    return lgamma_r((double)v + 1., &sg);
+  }
+  Hypergeom(uint64_t r1_, uint64_t r2_, uint64_t c1_) : r1(r1_), r2(r2_), c1(c1_) {
+    base = lg(r1) + lg(r2) + lg(c1) + lg(r1 + r2 - c1) - lg(r1 + r2);
+  }
+  double operator()(uint64_t x) const { return base - lg(x) - lg(r1 - x) - lg(c1 - x) - lg(r2 - c1 + x); }
+};
+
+// the records of one strand's grouped log, per site: (ids, count)
+using LogGroups = std::vector<std::vector<std::pair<AlleleIds, uint64_t>>>;
+
 }  // namespace
 
 struct gmx_infer {
   const gmx_index *ix = nullptr;
   std::unique_ptr<Genotyper> g;
+  bool strands = false;  // gmx_infer_annotate_strands has run: the writers add COV_FWD, COV_REV and SB
 };
 
 static int fail(const std::string &m, int code = GMX_EINVAL) {
   gmx_set_error(m);
   return code;
+}
+
+static int log_groups_of_sites(const gmx::HostIndex &h, const uint32_t *glog, uint64_t n_log, LogGroups &out) {
+  out.assign(h.sites.size(), {});
+  for (uint64_t i = 0; i < n_log;) {
+    if (glog[i] == 0xFFFFFFFFu) {
+      ++i;
+      continue;
+    }
+    if (i + 2 > n_log) break;
+    if (glog[i + 1] & GMX_LOG_REVERSE) return fail("gmx_infer_annotate_strands: a per-strand log has no GMX_LOG_REVERSE records");
+    const uint32_t s = glog[i], n = glog[i + 1] & ~GMX_LOG_COUNTED;
+    const uint64_t head = (glog[i + 1] & GMX_LOG_COUNTED) ? 4 : 2;
+    if (s >= h.sites.size() || i + head + n > n_log) return fail("corrupt grouped log");
+    const uint64_t count = head == 4 ? ((uint64_t)glog[i + 2] | ((uint64_t)glog[i + 3] << 32)) : 1;
+    for (uint64_t j = 0; j < n; ++j)
+      if (glog[i + head + j] >= h.sites[s].n_alleles) return fail("corrupt grouped log: an allele id beyond the site's alleles");
+    out[s].emplace_back(AlleleIds(glog + i + head, glog + i + head + n), count);
+    i += head + n;
+  }
+  return GMX_OK;
 }
 
 // grouped counts per site from the raw totals (dense slots + log), uint16 wrap as the reference's counters
@@ -979,6 +1042,130 @@ int64_t gmx_infer_debug_text(const gmx_infer *inf, char *out, uint64_t cap) try 
   if (out && cap > t.size()) memcpy(out, t.c_str(), t.size() + 1);
   return (int64_t)t.size();
 } GMX_GUARD_INT("gmx_infer_debug_text")
+
+double gmx_strand_bias_phred(uint64_t a, uint64_t b, uint64_t c, uint64_t d) try {
+  // Counts are taken as at most 2^40 each: lgamma's absolute error grows with its argument (about 3e-3 at 1e12, 1e-10 at the
+  // 1e5 of a deep sequencing run), and beyond that the score would be noise. The work does not grow with the counts' size but
+  // with the number of tables whose probability a double can still tell from zero beside the largest one summed — a few
+  // standard deviations' worth, ~sqrt(n) — plus two binary searches; nothing is allocated.
+  const uint64_t cap = 1ull << 40;
+  a = std::min(a, cap), b = std::min(b, cap), c = std::min(c, cap), d = std::min(d, cap);
+  const uint64_t r1 = a + b, r2 = c + d, c1 = a + c, c2 = b + d;
+  if (!r1 || !r2 || !c1 || !c2) return 0.;
+  const Hypergeom lp(r1, r2, c1);
+  const uint64_t lo = c1 > r2 ? c1 - r2 : 0, hi = std::min(r1, c1);
+  const double limit = lp(a) + log1p(1e-7);
+  // The probabilities rise up to the mode and fall after it, so the tables no more probable than the observed one are a left
+  // tail [lo, xl] and a right tail [xr, hi], one of them holding the observed table: two binary searches for their inner
+  // ends (the 1e-7 of the tie rule is far above the noise of lgamma, so a tie across the mode is found on both sides).
+  const uint64_t mode = std::min(hi, std::max(lo, (uint64_t)(((long double)r1 + 1) * ((long double)c1 + 1) / ((long double)r1 + (long double)r2 + 2))));
+  bool have_left = lp(lo) <= limit, have_right = lp(hi) <= limit;
+  uint64_t xl = lo, xr = hi;
+  if (have_left) {  // the last x of [lo, mode] with lp(x) <= limit
+    uint64_t l = lo, h = mode;
+    while (l < h) {
+      const uint64_t m = l + (h - l + 1) / 2;
+      if (lp(m) <= limit) l = m; else h = m - 1;
+    }
+    xl = l;
+  }
+  if (have_right && mode < hi) {  // the first x of [mode + 1, hi] with lp(x) <= limit
+    uint64_t l = mode + 1, h = hi;
+    while (l < h) {
+      const uint64_t m = l + (h - l) / 2;
+      if (lp(m) <= limit) h = m; else l = m + 1;
+    }
+    xr = l;
+  } else {
+    have_right = false;  // (mode == hi: the left search covered every table)
+  }
+  if (have_left && xl == mode && (mode == hi || (have_right && xr == mode + 1))) return 0.;  // every table: p = 1
+  // log of the sum relative to its largest term (an inner end): a probability far below the smallest double keeps its score.
+  // A tail is left where its terms no longer change the sum (exp of less than -745 is zero).
+  const double top = std::max(have_left ? lp(xl) : -INFINITY, have_right ? lp(xr) : -INFINITY);
+  double sum = 0.;
+  if (have_left)
+    for (uint64_t x = xl;; --x) {
+      const double t = lp(x) - top;
+      if (t < -745.) break;
+      sum += exp(t);
+      if (x == lo) break;
+    }
+  if (have_right)
+    for (uint64_t x = xr; x <= hi; ++x) {
+      const double t = lp(x) - top;
+      if (t < -745.) break;
+      sum += exp(t);
+    }
+  const double log_p = top + log(sum);
+  if (!(log_p < 0.)) return 0.;
+  return -10. * log_p / M_LN10;
+} GMX_GUARD_ZERO("gmx_strand_bias_phred")
+
+int gmx_infer_annotate_strands(gmx_infer *inf, const uint32_t *grouped_dense_fwd, const uint32_t *grouped_dense_rev,
+                               const uint32_t *log_fwd, uint64_t n_log_fwd, const uint32_t *log_rev, uint64_t n_log_rev) try {
+  if (!inf || !inf->g || (!log_fwd && n_log_fwd) || (!log_rev && n_log_rev)) return fail("gmx_infer_annotate_strands: null argument");
+  Genotyper &g = *inf->g;
+  const gmx::HostIndex &h = g.h;
+  if (h.n_grouped_slots && (!grouped_dense_fwd || !grouped_dense_rev)) return fail("gmx_infer_annotate_strands: null dense grouped counts");
+  LogGroups lg[2];
+  {
+    int rc = log_groups_of_sites(h, log_fwd, n_log_fwd, lg[0]);
+    if (!rc) rc = log_groups_of_sites(h, log_rev, n_log_rev, lg[1]);
+    if (rc) return rc;
+  }
+  const uint32_t *dense[2] = {grouped_dense_fwd, grouped_dense_rev};
+  par_ranges(g.recs.size(), 512, [&](size_t b, size_t e, size_t) {
+    std::vector<uint64_t> hap[2];
+    std::vector<uint8_t> in_call;
+    for (size_t si = b; si < e; ++si) {
+      Site &s = *g.recs[si];
+      s.has_strands = true;
+      s.cov_fwd.clear();
+      s.cov_rev.clear();
+      s.sb = 0.;
+      if (s.is_null()) continue;
+      const uint32_t n = h.sites[si].n_alleles;
+      in_call.assign(n, 0);
+      for (int32_t hg : s.haplogroups)
+        if (hg >= 0 && (uint32_t)hg < n) in_call[hg] = 1;
+      uint64_t called[2] = {0, 0}, other[2] = {0, 0};
+      for (int st = 0; st < 2; ++st) {
+        hap[st].assign(n, 0);
+        if (h.l_grouped_off[si] != GMX_GROUPED_LOG) {
+          const uint32_t nm = (1u << n) - 1u;
+          for (uint32_t m = 0; m < nm; ++m) {
+            const uint64_t count = dense[st][h.l_grouped_off[si] + m];
+            if (!count) continue;
+            bool hit = false;
+            for (uint32_t a = 0; a < n; ++a)
+              if (((m + 1) >> a) & 1u) {
+                hap[st][a] += count;
+                hit = hit || in_call[a];
+              }
+            (hit ? called : other)[st] += count;
+          }
+        }
+        for (auto const &rec : lg[st][si]) {  // (a site has dense slots or log records)
+          bool hit = false;
+          for (int32_t a : rec.first) {
+            hap[st][a] += rec.second;
+            hit = hit || in_call[a];
+          }
+          (hit ? called : other)[st] += rec.second;
+        }
+      }
+      for (auto const &al : s.alleles) {
+        const bool known = al.hapg >= 0 && (uint32_t)al.hapg < n;
+        s.cov_fwd.push_back(known ? hap[0][al.hapg] : 0);
+        s.cov_rev.push_back(known ? hap[1][al.hapg] : 0);
+      }
+      s.sb = gmx_strand_bias_phred(called[0], called[1], other[0], other[1]);
+    }
+  });
+  inf->strands = true;
+  return GMX_OK;
+} GMX_GUARD_INT("gmx_infer_annotate_strands")
 
 int64_t gmx_infer_site_json(const gmx_infer *inf, uint32_t site_index, char *out, uint64_t cap) try {
   if (!inf || site_index >= inf->g->recs.size()) return fail("gmx_infer_site_json: bad argument");
@@ -1333,11 +1520,13 @@ int gmx_infer_write_json(const gmx_infer *inf, const char *coords_path, const ch
   }
   o << "],\"Model\":\"LevelGenotyping\",\"Samples\":[{\"Desc\":\"made by gramtools genotype\",\"Name\":" << jstr(sample_id ? sample_id : "")
     << "}],\"Site_Fields\":{\"ALS\":{\"Desc\":\"Alleles at this site\"},\"COV\":{\"Desc\":\"Read coverage on each allele\"},"
-       "\"DP\":{\"Desc\":\"Total read depth on variant site\"},\"FT\":{\"Desc\":\"Filters failed in a sample\"},"
+           << (inf->strands ? "\"COV_FWD\":{\"Desc\":" + jstr(kCovFwdDesc) + "},\"COV_REV\":{\"Desc\":" + jstr(kCovRevDesc) + "}," : std::string())
+    << "\"DP\":{\"Desc\":\"Total read depth on variant site\"},\"FT\":{\"Desc\":\"Filters failed in a sample\"},"
        "\"GT\":{\"Desc\":\"Genotype\"},\"GT_CONF\":{\"Desc\":"
     << jstr(kGtConfDesc) << "},\"GT_CONF_PERCENTILE\":{\"Desc\":" << jstr(kGcpDesc)
     << "},\"HAPG\":{\"Desc\":\"Sample haplogroups of genotyped alleles\"},\"POS\":{\"Desc\":\"Position on reference or pseudo-reference\"},"
-       "\"SEG\":{\"Desc\":\"Segment ID\"}},\"Sites\":[";
+    << (inf->strands ? "\"SB\":{\"Desc\":" + jstr(kSbDesc) + "}," : std::string())
+    << "\"SEG\":{\"Desc\":\"Segment ID\"}},\"Sites\":[";
   {  // the records formatted side by side (each range with a tracker of its own: positions ascend within a range), written in order
     const size_t n = g.recs.size();
     std::vector<std::string> part(par_parts(n, 2048));
@@ -1381,8 +1570,12 @@ int gmx_infer_write_vcf(const gmx_infer *inf, const char *coords_path, const cha
      << "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\",Source=\"gramtools\">\n"
      << "##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Total read depth on variant site\",Source=\"gramtools\">\n"
      << "##FORMAT=<ID=COV,Number=R,Type=Float,Description=\"Read coverage on each allele\",Source=\"gramtools\">\n"
-     << "##FORMAT=<ID=FT,Number=1,Type=String,Description=\"Filters failed in a sample\",Source=\"gramtools\">\n"
-     << "##FILTER=<ID=AMBIG,Description=\"" << kAmbigDesc << "\",Source=\"gramtools\">\n"
+     << "##FORMAT=<ID=FT,Number=1,Type=String,Description=\"Filters failed in a sample\",Source=\"gramtools\">\n";
+  if (inf->strands)
+    hd << "##FORMAT=<ID=COV_FWD,Number=R,Type=Integer,Description=\"" << kCovFwdDesc << "\",Source=\"gramtools\">\n"
+       << "##FORMAT=<ID=COV_REV,Number=R,Type=Integer,Description=\"" << kCovRevDesc << "\",Source=\"gramtools\">\n"
+       << "##FORMAT=<ID=SB,Number=1,Type=Float,Description=\"" << kSbDesc << "\",Source=\"gramtools\">\n";
+  hd << "##FILTER=<ID=AMBIG,Description=\"" << kAmbigDesc << "\",Source=\"gramtools\">\n"
      << "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" << (sample_id ? sample_id : "sample") << "\n";
   z.write(hd.str());
   const size_t n_recs = g.recs.size();
@@ -1408,7 +1601,7 @@ int gmx_infer_write_vcf(const gmx_infer *inf, const char *coords_path, const cha
     else
       for (size_t a = 1; a < s.alleles.size(); ++a) r << (a > 1 ? "," : "") << s.alleles[a].seq;
     const bool has_cov = !s.covs.empty();
-    r << "\t.\t.\t.\tGT:DP" << (has_cov ? ":COV" : "") << ":FT:GT_CONF:GT_CONF_PERCENTILE\t";
+    r << "\t.\t.\t.\tGT:DP" << (has_cov ? ":COV" : "") << ":FT:GT_CONF:GT_CONF_PERCENTILE" << (s.has_strands ? ":COV_FWD:COV_REV:SB" : "") << "\t";
     if (s.is_null())
       r << ".";
     else
@@ -1423,7 +1616,19 @@ int gmx_infer_write_vcf(const gmx_infer *inf, const char *coords_path, const cha
       r << "PASS";
     else  // the reference hands htslib only the first string of the vector (make_vcf.cpp:124-134)
       r << s.filters[0] << (s.filters.size() > 1 ? "," : "");
-    r << ":" << fmt_g(s.gt_conf) << ":" << fmt_g(s.gt_conf_percentile) << "\n";
+    r << ":" << fmt_g(s.gt_conf) << ":" << fmt_g(s.gt_conf_percentile);
+    if (s.has_strands) {
+      if (s.is_null()) {
+        r << ":.:.:.";
+      } else {
+        r << ":";
+        for (size_t k = 0; k < s.cov_fwd.size(); ++k) r << (k ? "," : "") << s.cov_fwd[k];
+        r << ":";
+        for (size_t k = 0; k < s.cov_rev.size(); ++k) r << (k ? "," : "") << s.cov_rev[k];
+        r << ":" << fmt_g(s.sb);
+      }
+    }
+    r << "\n";
     acc += r.str();
   }
   });

@@ -86,7 +86,13 @@ const char *kGenotypeHelp =
     "                              what their reverse complements recorded, in the formats of allele_sum_coverage and\n"
     "                              allele_base_coverage.json but as RAW totals (no 16-bit wrap, no saturation): entry by entry\n"
     "                              forward + reverse = allele_sum_coverage (mod 65536) and min(forward + reverse, 65535) =\n"
-    "                              allele_base_coverage.json. Grouped allele counts are not split\n";
+    "                              allele_base_coverage.json. No grouped allele counts file per strand is written\n"
+    "  --strand_bias               strand evidence in the calls (engine extension): genotyped.json and genotyped.vcf.gz gain, per\n"
+    "                              site, COV_FWD and COV_REV — per allele, the reads as given and the reverse complements among\n"
+    "                              the grouped allele counts that contain its haplogroup (raw totals) — and SB, the phred-scaled\n"
+    "                              two-sided Fisher exact probability of the table (called haplogroups, all others) x (forward,\n"
+    "                              reverse); in the VCF they are the last three FORMAT fields, `.:.:.` at a null call. Every other\n"
+    "                              field and file stays as it is; no filter is applied\n";
 
 [[noreturn]] void die(const std::string &msg, int code = 1) {
   std::cout << msg << std::endl;
@@ -2209,7 +2215,9 @@ int run_genotype(const Args &a) {
   // --strand_coverage: every engine keeps the reads' and their reverse complements' coverage apart, across samples (a reset
   // zeroes both blocks); the exchange carries both
   const bool strand_coverage = a.has("strand_coverage");
-  if (strand_coverage) GMX_CHECK(gmx_group_record_strands(grp, 1));
+  // --strand_bias: the same recording; the infer stage reads both strands' grouped counts (gmx_infer_annotate_strands)
+  const bool strand_bias = a.has("strand_bias");
+  if (strand_coverage || strand_bias) GMX_CHECK(gmx_group_record_strands(grp, 1));
   auto note_outcomes = [&](int engine, uint64_t n) {  // BEFORE the call that hands n reads to `engine` (or to the group)
     if (!read_outcomes || n == 0) return;
     const int64_t at = engine < 0 ? gmx_group_outcome_count(grp) : gmx_engine_outcome_count(gmx_group_engine(grp, engine));
@@ -2434,6 +2442,18 @@ int run_genotype(const Args &a) {
       GMX_CHECK(gmx_coverage_fetch_strand(eng, sd, strand_allele_sum[sd].data(), strand_per_base[sd].data(), nullptr));
     }
 
+  std::vector<uint32_t> strand_grouped[2], strand_log[2];  // --strand_bias: raw grouped counts per strand, dense slots and log
+  if (strand_bias)
+    for (int sd = 0; sd < 2; ++sd) {
+      strand_grouped[sd].assign(grouped.size(), 0);
+      GMX_CHECK(gmx_coverage_fetch_strand(eng, sd, nullptr, nullptr, strand_grouped[sd].data()));
+      const int64_t n = gmx_coverage_fetch_grouped_log_strand(eng, sd, nullptr, 0);
+      if (n < 0) die(std::string("gram: grouped log per strand: ") + gmx_last_error());
+      strand_log[sd].assign((size_t)n, 0);
+      if (n && gmx_coverage_fetch_grouped_log_strand(eng, sd, strand_log[sd].data(), (uint64_t)n) != n)
+        die(std::string("gram: grouped log per strand: ") + gmx_last_error());
+    }
+
   gmx_depth_stats ds;  // readstats.compute_coverage_depth, quasimap.cpp:48
   GMX_CHECK(gmx_compute_coverage_depth(ix, per_base.data(), grouped.data(), glog.data(), (uint64_t)n_log, &ds));
   rs.mean_cov_depth = ds.mean_cov_depth;
@@ -2610,6 +2630,9 @@ int run_genotype(const Args &a) {
   gmx_infer *inf = nullptr;
   GMX_CHECK(gmx_infer_run(ix, per_base.data(), grouped.data(), glog.data(), (uint64_t)n_log, rs.mean_cov_depth, rs.variance_cov_depth,
                           rs.mean_pb_error, ploidy == "haploid" ? 1 : 2, &inf));
+  if (strand_bias)
+    GMX_CHECK(gmx_infer_annotate_strands(inf, strand_grouped[0].data(), strand_grouped[1].data(), strand_log[0].data(), strand_log[0].size(),
+                                         strand_log[1].data(), strand_log[1].size()));
   const std::string coords = join(gram_dir, "prg_coords.tsv");
   if (a.has("debug")) {  // site_gtyping_debug_info.txt (parameters.cpp:98; genotype.cpp:76-82)
     const std::string dbg_path = join(run_dir, "site_gtyping_debug_info.txt");

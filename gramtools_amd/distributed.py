@@ -116,7 +116,7 @@ def allreduce_device_coverage(qm, dist, tensor=None, stream=None):
     qm.reduce_end(stream)
     if qm.index.uses_grouped_log and dist.get_world_size() > 1:
         logs = [None] * dist.get_world_size()
-        dist.all_gather_object(logs, qm.grouped_log())
+        dist.all_gather_object(logs, qm.export_grouped_log())  # (with record_strands: both strands' records)
         for r, log in enumerate(logs):
             qm.import_grouped_log(np.asarray(log, dtype=np.uint32), replace=(r == 0))
 

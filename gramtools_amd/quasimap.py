@@ -316,6 +316,12 @@ class Coverage:
         self.allele_sum_flat = (allele_sum_u32 & 0xFFFF).astype(np.uint16)             # wraps, data_types.hpp:52
         self.per_base_flat = np.minimum(per_base_u32, 65535).astype(np.uint16)           # saturates, allele_base.cpp:239
 
+    def with_grouped_log(self, grouped_log) -> "Coverage":
+        """This coverage with another grouped log: a strand's Coverage (Quasimapper.coverage(strand=s), whose log is empty)
+        plus Quasimapper.grouped_log(strand=s) has that strand's grouped counts at every site."""
+        return Coverage(self.index, self.raw_allele_sum, self.raw_per_base, self.raw_grouped,
+                        np.asarray(grouped_log, dtype=np.uint32), self.stats)
+
     # AlleleSumCoverage: vector (per site) of vector (per allele)
     @property
     def allele_sum_coverage(self):
@@ -431,18 +437,20 @@ def dump_grouped_allele_counts(cov: Coverage) -> str:
 
 
 LOG_COUNTED = 0x80000000
+LOG_REVERSE = 0x40000000  # exchange form only: the record counts reverse-complement tasks (gmx.h, GMX_LOG_REVERSE)
 LOG_PAD = 0xFFFFFFFF
 
 
 def iter_grouped_log(log):
     """(site_index, ids, count) of every record of a grouped log (gmx.h, gmx_coverage_fetch_grouped_log): records worth
-    +1 ``[site, n, ids...]`` or +count ``[site, n | LOG_COUNTED, count_lo, count_hi, ids...]``; the same key may recur."""
+    +1 ``[site, n, ids...]`` or +count ``[site, n | LOG_COUNTED, count_lo, count_hi, ids...]``; the same key may recur. In
+    the exchange form (Quasimapper.export_grouped_log) a record's strand bit is dropped: both strands' records are yielded."""
     i, n_words = 0, len(log)
     while i < n_words:
         if int(log[i]) == LOG_PAD:
             i += 1
             continue
-        s, n = int(log[i]), int(log[i + 1])
+        s, n = int(log[i]), int(log[i + 1]) & ~LOG_REVERSE
         head, count = 2, 1
         if n & LOG_COUNTED:
             n &= ~LOG_COUNTED
@@ -671,17 +679,31 @@ class Quasimapper:
         check(self.lib.gmx_coverage_import_grouped_log(self.h, _p(r if r.size else np.zeros(1, np.uint32), C.c_uint32), r.size,
                                                        1 if replace else 0))
 
-    def grouped_log(self):
-        n = check(self.lib.gmx_coverage_fetch_grouped_log(self.h, None, 0))
+    def _fetch_log(self, fn, *args):
+        n = check(fn(self.h, *args, None, 0))
         log = np.zeros(max(n, 1), dtype=np.uint32)
         if n:
-            check(self.lib.gmx_coverage_fetch_grouped_log(self.h, _p(log, C.c_uint32), n))
+            check(fn(self.h, *args, _p(log, C.c_uint32), n))
         return log[:n]
+
+    def grouped_log(self, strand=None):
+        """Counted records of the sites on the grouped log: the totals, or with ``strand`` 0 (forward) / 1 (reverse
+        complement) that strand's records (record_strands; gmx_coverage_fetch_grouped_log_strand), in the same form."""
+        if strand is None:
+            return self._fetch_log(self.lib.gmx_coverage_fetch_grouped_log)
+        if strand not in (0, 1):
+            raise ValueError("strand is None (totals), 0 (forward) or 1 (reverse complement)")
+        return self._fetch_log(self.lib.gmx_coverage_fetch_grouped_log_strand, int(strand))
+
+    def export_grouped_log(self):
+        """The log as engines exchange it (import_grouped_log takes it): with record_strands up to two records per key, the
+        reverse-complement one with LOG_REVERSE; otherwise grouped_log()."""
+        return self._fetch_log(self.lib.gmx_coverage_export_grouped_log)
 
     def coverage(self, strand=None) -> Coverage:
         """The totals, or with ``strand`` 0 (forward) / 1 (reverse complement) one strand's share of them (record_strands;
-        gmx_coverage_fetch_strand). A strand's Coverage carries an empty grouped log — the log is not split — and the read
-        counters of the whole run."""
+        gmx_coverage_fetch_strand). A strand's Coverage carries an empty grouped log (grouped_log(strand) has that strand's
+        records; Coverage.with_grouped_log attaches them) and the read counters of the whole run."""
         info = self.index.info
         a = np.zeros(max(info.n_allele_slots, 1), dtype=np.uint32)
         p = np.zeros(max(info.n_per_base_slots, 1), dtype=np.uint32)
@@ -940,15 +962,35 @@ class QuasimapperGroup:
         check(self.lib.gmx_group_fetch_outcomes(self.h, first, n, _p(out, C.c_uint8)))
         return out[:n]
 
+    def _member(self, member: int) -> Quasimapper:
+        view = Quasimapper.__new__(Quasimapper)
+        view.lib, view.index, view.h = self.lib, self.index, C.c_void_p(self.lib.gmx_group_engine(self.h, member))
+        return view
+
     def coverage(self, member: int = 0, strand=None) -> Coverage:
         """Coverage held by engine `member` (after :meth:`allreduce`: the totals of the whole job, on every member); with
         ``strand`` 0 / 1 one strand's share (record_strands)."""
-        view = Quasimapper.__new__(Quasimapper)
-        view.lib, view.index, view.h = self.lib, self.index, C.c_void_p(self.lib.gmx_group_engine(self.h, member))
+        view = self._member(member)
         try:
             return view.coverage(strand)
         finally:
             view.h = None  # the group owns the engine
+
+    def grouped_log(self, member: int = 0, strand=None):
+        """Quasimapper.grouped_log of engine `member`."""
+        view = self._member(member)
+        try:
+            return view.grouped_log(strand)
+        finally:
+            view.h = None
+
+    def export_grouped_log(self, member: int = 0):
+        """Quasimapper.export_grouped_log of engine `member`."""
+        view = self._member(member)
+        try:
+            return view.export_grouped_log()
+        finally:
+            view.h = None
 
 
 class Genotyped:
@@ -975,6 +1017,14 @@ class Genotyped:
             self.h = None
 
     __del__ = close
+
+    def annotate_strands(self, cov_fwd: Coverage, cov_rev: Coverage):
+        """Strand evidence of the calls (gmx_infer_annotate_strands): site() and the written files gain COV_FWD, COV_REV and
+        SB. The two strands' coverage WITH their logs: ``qm.coverage(strand=s).with_grouped_log(qm.grouped_log(strand=s))``."""
+        arr = lambda x: np.ascontiguousarray(x if x.size else np.zeros(1, np.uint32), dtype=np.uint32)
+        gf, gr, lf, lr = arr(cov_fwd.raw_grouped), arr(cov_rev.raw_grouped), arr(cov_fwd.raw_grouped_log), arr(cov_rev.raw_grouped_log)
+        check(self.lib.gmx_infer_annotate_strands(self.h, _p(gf, C.c_uint32), _p(gr, C.c_uint32), _p(lf, C.c_uint32),
+                                                  cov_fwd.raw_grouped_log.size, _p(lr, C.c_uint32), cov_rev.raw_grouped_log.size))
 
     def site(self, i: int) -> dict:
         n = check(self.lib.gmx_infer_site_json(self.h, i, None, 0))

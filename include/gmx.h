@@ -525,9 +525,10 @@ int gmx_engine_fetch_outcomes(gmx_engine *e, uint64_t first, uint64_t n, uint8_t
 /* Coverage per strand (off by default; nothing changes while it is off). Every read is mapped as given and reverse-complemented;
  * with recording on, the engine keeps TWO accumulator blocks — what the reads as given added, and what their reverse complements
  * added — instead of one: allele-sum, dense grouped counts and per-base counts of every site, each per strand. The read counters
- * are not split. The grouped log (sites with more than 8 alleles, gmx_coverage_fetch_grouped_log) is NOT split either: such a
- * site's allele-sum and per-base counts are per strand, its grouped counts are totals only. With gmx_engine_opts::forward_only
- * the reverse block stays zero.
+ * are not split. The grouped log (sites with more than 8 alleles) is split too: a record of a reverse-complement task carries
+ * GMX_LOG_REVERSE in its second word on the device, the engine keeps two counts per distinct (site, ids), and
+ * gmx_coverage_fetch_grouped_log_strand returns one strand's (gmx_coverage_fetch_grouped_log: their sums, as with recording
+ * off). With gmx_engine_opts::forward_only the reverse block stays zero and the reverse log empty.
  *   gmx_engine_record_strands  may only be called while nothing is recorded — after gmx_engine_create, gmx_engine_reset or a
  *     gmx_engine_reset_async (it waits for the engine's work) — and returns GMX_EINVAL otherwise. It gives the engine its one-block
  *     or two-block allocation; when that fails it returns the error's code, the mode and the old block unchanged.
@@ -546,16 +547,30 @@ int gmx_coverage_fetch_strand(gmx_engine *e, int strand, uint32_t *allele_sum, u
  *   [site_index, n_ids, ids...]                                     worth +1, or
  *   [site_index, n_ids | GMX_LOG_COUNTED, count_lo, count_hi, ids...] worth +count,
  * ids ascending; the same (site, ids) may appear in several records (their values add up — concatenating the logs of
- * several engines is their sum). This function returns counted records, one per distinct (site, ids). */
+ * several engines is their sum). This function returns counted records, one per distinct (site, ids), worth the total
+ * of both strands, never with GMX_LOG_REVERSE.
+ * GMX_LOG_REVERSE (bit 30 of a record's second word, either form): the record counts reverse-complement tasks. Only an
+ * engine that records strands (gmx_engine_record_strands) writes it, and only the device log and the exchange form (what
+ * the multi-GPU exchange and gramtools_amd/distributed.py pass between engines: up to two counted records per distinct
+ * (site, ids), the reverse one with the bit) carry it. n_ids is the second word without both flag bits. */
 #define GMX_LOG_COUNTED 0x80000000u
+#define GMX_LOG_REVERSE 0x40000000u
 int64_t gmx_coverage_fetch_grouped_log(gmx_engine *e, uint32_t *out, uint64_t cap_words);
-/* Adds the records of a grouped log (either form) to the engine's totals, after emptying them when `replace`: the
- * receiving end of a log exchange done outside the library (gramtools_amd/distributed.py under torch.distributed). */
+/* One strand's counted records (strand 0: forward, 1: reverse complement), in the same form without GMX_LOG_REVERSE — whatever
+ * parses the totals parses these; a record appears only where that strand's count is non-zero. GMX_EINVAL while recording is
+ * off or for another strand. */
+int64_t gmx_coverage_fetch_grouped_log_strand(gmx_engine *e, int strand, uint32_t *out, uint64_t cap_words);
+/* The engine's log in the exchange form: with recording off, the records of gmx_coverage_fetch_grouped_log. */
+int64_t gmx_coverage_export_grouped_log(gmx_engine *e, uint32_t *out, uint64_t cap_words);
+/* Adds the records of a grouped log (either form, with or without GMX_LOG_REVERSE) to the engine's totals, after emptying them
+ * when `replace`: the receiving end of a log exchange done outside the library (gramtools_amd/distributed.py under
+ * torch.distributed). A record with GMX_LOG_REVERSE for an engine that does not record strands: GMX_EINVAL, nothing changed. */
 int gmx_coverage_import_grouped_log(gmx_engine *e, const uint32_t *records, uint64_t n_words, int replace);
 /* The receiving end of the log exchange as a pure function (used by gmx_group_allreduce / gmx_comm_allreduce_coverage after
  * their payload all-gather; exported for the tests): `gathered` = world slices of `pad` words, slice r holding sizes[r] words
- * of rank r's log (an empty rank: 0). Returns the length of the merged log (counted records, one per distinct (site, ids))
- * and copies it when it fits cap_words. */
+ * of rank r's log (an empty rank: 0). Returns the length of the merged log (counted records, one per distinct (site, ids)
+ * and strand: GMX_LOG_REVERSE is part of the merge key and set again on output, the forward record first) and copies it
+ * when it fits cap_words. */
 int64_t gmx_grouped_log_merge_gathered(const uint32_t *gathered, const uint64_t *sizes, int world, uint64_t pad, uint32_t *out,
                                        uint64_t cap_words);
 void gmx_finalize_u16(uint32_t *values, uint64_t n, int saturate);
@@ -581,6 +596,24 @@ int gmx_infer_write_fasta(const gmx_infer *inf, const char *coords_path, const c
 int64_t gmx_infer_debug_text(const gmx_infer *inf, char *out, uint64_t cap);
 /* One site as its jVCF object (POS 1-based in PRG coordinates); returns the length, copies when it fits cap. */
 int64_t gmx_infer_site_json(const gmx_infer *inf, uint32_t site_index, char *out, uint64_t cap);
+/* Strand evidence of the calls (`gram genotype --strand_bias`), after gmx_infer_run: the per-strand RAW dense grouped counts of
+ * gmx_coverage_fetch_strand and the per-strand logs of gmx_coverage_fetch_grouped_log_strand (no 16-bit wrap, sums in 64 bits).
+ * Every site whose genotype is not null gets
+ *   COV_FWD[i], COV_REV[i]  per output allele (the order of ALS / COV): that strand's grouped counts summed over every group
+ *                           that contains the allele's haplogroup (the haploid coverage of the model, per strand);
+ *   SB                      gmx_strand_bias_phred(called_fwd, called_rev, other_fwd, other_rev): called = the groups that share
+ *                           a haplogroup with the called genotype, other = the groups disjoint from it (groups are disjoint
+ *                           classes of mapped tasks). Nested sites use their own counts and calls.
+ * The writers and gmx_infer_site_json then add the three fields (jVCF: keys COV_FWD, COV_REV, SB, null site SB [null] and empty
+ * lists; VCF: FORMAT ...:COV_FWD:COV_REV:SB at the end, a null site `.:.:.`); without this call they write what they wrote. */
+int gmx_infer_annotate_strands(gmx_infer *inf, const uint32_t *grouped_dense_fwd, const uint32_t *grouped_dense_rev,
+                               const uint32_t *log_fwd, uint64_t n_log_fwd, const uint32_t *log_rev, uint64_t n_log_rev);
+/* -10 log10 of the two-sided Fisher exact probability of the table [[a, b], [c, d]] (the hypergeometric probabilities of all
+ * tables with its margins that are at most P(observed) (1 + 1e-7), summed; capped at 1). +0.0 when p = 1 or a margin is zero.
+ * Counts above 2^40 are taken as 2^40 (the log-gamma sums lose their digits beyond; within 1e-6 of the exact value for
+ * counts up to 1e5, which the tests pin). No allocation; the work grows with the width of the distribution (~sqrt of the
+ * total), not with the counts. */
+double gmx_strand_bias_phred(uint64_t a, uint64_t b, uint64_t c, uint64_t d);
 /* The likelihood model on explicit alleles and grouped counts (the known answers of tests/genotype/infer/
  * level_genotyping/test_model.cpp): the resulting site as JSON with the model's extra alleles and thresholds. */
 int64_t gmx_infer_model(uint32_t n_alleles, const char *const *seqs, const uint32_t *pb_off, const uint32_t *pb_cov,
