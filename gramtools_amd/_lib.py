@@ -161,6 +161,9 @@ SYMBOLS = {
     "gmx_engine_record_outcomes": (C.c_int, [_vp, C.c_int]),
     "gmx_engine_outcome_count": (_i64, [_vp]),
     "gmx_engine_fetch_outcomes": (C.c_int, [_vp, _u64, _u64, _u8p]),
+    "gmx_engine_record_positions": (C.c_int, [_vp, C.c_int]),
+    "gmx_engine_position_count": (_i64, [_vp]),
+    "gmx_engine_fetch_positions": (C.c_int, [_vp, _u64, _u64, _u32p]),
     "gmx_engine_record_strands": (C.c_int, [_vp, C.c_int]),
     "gmx_coverage_fetch_strand": (C.c_int, [_vp, C.c_int, _u32p, _u32p, _u32p]),
     "gmx_coverage_fetch_grouped_log_strand": (_i64, [_vp, C.c_int, _u32p, _u64]),
@@ -196,6 +199,9 @@ SYMBOLS = {
     "gmx_group_allreduce": (C.c_int, [_vp]),
     "gmx_group_outcome_count": (_i64, [_vp]),
     "gmx_group_fetch_outcomes": (C.c_int, [_vp, _u64, _u64, _u8p]),
+    "gmx_group_record_positions": (C.c_int, [_vp, C.c_int]),
+    "gmx_group_position_count": (_i64, [_vp]),
+    "gmx_group_fetch_positions": (C.c_int, [_vp, _u64, _u64, _u32p]),
     "gmx_group_record_strands": (C.c_int, [_vp, C.c_int]),
     "gmx_comm_unique_id": (C.c_int, [_u8p]),
     "gmx_comm_create": (C.c_int, [_u8p, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),

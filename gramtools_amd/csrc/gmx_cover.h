@@ -1139,7 +1139,7 @@ GMX_HD void gmx_class_record(const GmxIndexView &ix, Env &env, uint32_t n_loci, 
 // The items of a task's final states (handle_allele_encapsulated_states, encapsulated_search.cpp:30-107): a path-bearing
 // state as it is; a path-less one position by position — inside an allele it becomes a state of its own with that locus
 // as its path (add_item(lo, hi, traversed, traversing, site, allele)), outside every site it only counts
-// (nonvariant(position index): count_nonvar_search_states, coverage_common.cpp:130-141). The reference merges neighbouring
+// (nonvariant(position index, PRG position): count_nonvar_search_states, coverage_common.cpp:130-141). The reference merges neighbouring
 // positions of one allele into an interval; position by position is the same set of mapping instances.
 // false: add_item refused (scratch full). Used by gmx_cover_task and by the test hook gmx_debug_encapsulate.
 // ---------------------------------------------------------------------------
@@ -1152,9 +1152,10 @@ GMX_HD bool gmx_final_items(const GmxIndexView &ix, const GmxFinalState *finals,
       continue;
     }
     for (uint32_t i = st.lo;; ++i) {
-      const GmxNode &nd = ix.nodes[ix.pos_node[gmx_occ_pos(ix, st.hi, i)]];
+      const uint32_t p = gmx_occ_pos(ix, st.hi, i);
+      const GmxNode &nd = ix.nodes[ix.pos_node[p]];
       if (nd.site == 0)
-        nonvariant(i);
+        nonvariant(i, p);
       else if (!add_item(i, gmx_text_form(st.hi) ? st.hi : i, GMX_NIL, GMX_NIL, nd.site, nd.allele))
         return false;
       if (gmx_text_form(st.hi) || i == st.hi) break;
@@ -1163,15 +1164,48 @@ GMX_HD bool gmx_final_items(const GmxIndexView &ix, const GmxFinalState *finals,
   return true;
 }
 
+// The number of mapping instances of a task (the position record's n): one per suffix-array index of every final state, a
+// text-form state counting one; saturates at 0xFFFFFFFF.
+GMX_HD uint32_t gmx_count_instances(const GmxFinalState *finals, uint32_t n_final) {
+  uint64_t n = 0;
+  for (uint32_t f = 0; f < n_final; ++f) n += gmx_text_form(finals[f].hi) ? 1ull : (uint64_t)(finals[f].hi - finals[f].lo) + 1ull;
+  return n > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)n;
+}
+// The smallest PRG position among the instances lo .. hi of one state or item
+GMX_HD uint32_t gmx_min_occ_pos(const GmxIndexView &ix, uint32_t lo, uint32_t hi) {
+  uint32_t m = 0xFFFFFFFFu;
+  for (uint32_t i = lo;; ++i) {
+    const uint32_t p = gmx_occ_pos(ix, hi, i);
+    m = p < m ? p : m;
+    if (gmx_text_form(hi) || i == hi) break;
+  }
+  return m;
+}
+
+// A task's position record as gmx_cover_task reports it (the caller stores it once the task has succeeded). `on` is the caller's
+// switch: a caller that keeps the struct in registers passes its address whether or not it records.
+struct GmxWhere {
+  uint32_t pos, n;
+  bool on;
+};
+
 // ---------------------------------------------------------------------------
 // The whole recording step for one mapped task.
 // ---------------------------------------------------------------------------
 template <class Env>
 GMX_HD void gmx_cover_task(const GmxIndexView &ix, Env &env, const GmxFinalState *finals, uint32_t n_final,
-                           uint32_t read_len, uint32_t seed, int rng_mode, uint32_t *drawn_from = nullptr) {
+                           uint32_t read_len, uint32_t seed, int rng_mode, uint32_t *drawn_from = nullptr, GmxWhere *where = nullptr) {
   // drawn_from (optional): how many mapping instances the selection drew from (0: it did not draw)
+  // where (optional; filled when where->on): the task's position record, valid when the task ends with env.status ==
+  //   GMX_TASK_MAPPED — pos: the smallest PRG position among the instances the selection chose from (all of them when there is
+  //   no class, the non-variant ones when the draw fell on them, else those of the drawn class's items), n: gmx_count_instances
+  const bool want_where = where != nullptr && where->on;
   typedef GmxScratch<Env> S;
   if (n_final == 1 && (finals[0].lo == finals[0].hi || gmx_text_form(finals[0].hi))) {
+    if (want_where) {  // (one instance, whichever routine records it)
+      where->pos = gmx_occ_pos(ix, finals[0].hi, finals[0].lo);
+      where->n = 1u;
+    }
     if (!ix.is_nested) {
       gmx_cover_single(ix, env, finals[0], read_len);
       return;
@@ -1197,8 +1231,17 @@ GMX_HD void gmx_cover_task(const GmxIndexView &ix, Env &env, const GmxFinalState
     ++n_items;
     return true;
   };
-  if (!gmx_final_items(ix, finals, n_final, add_item, [&](uint32_t) { nonvariant += 1; })) return;
+  uint32_t nonvar_min = 0xFFFFFFFFu;  // the smallest PRG position of a non-variant instance (the position record)
+  if (!gmx_final_items(ix, finals, n_final, add_item, [&](uint32_t, uint32_t p) {
+        nonvariant += 1;
+        nonvar_min = p < nonvar_min ? p : nonvar_min;
+      }))
+    return;
   GMX_COVER_PROF(env, 0);
+  if (want_where) {  // (no class, or the draw falls on the non-variant instances: those; a drawn class replaces it below)
+    where->pos = nonvar_min;
+    where->n = gmx_count_instances(finals, n_final);
+  }
   if (n_items == 0) return;  // usps.size() == 0: nothing recorded, no draw (coverage_common.cpp:96-97)
 
   // --- class keys ---
@@ -1271,6 +1314,15 @@ GMX_HD void gmx_cover_task(const GmxIndexView &ix, Env &env, const GmxFinalState
       env.fail(GMX_TASK_ERROR);
       return;
     }
+  }
+  if (want_where) {  // the drawn class's instances (the item records are still in the scratch: gmx_class_record reuses their words)
+    uint32_t m = 0xFFFFFFFFu;
+    for (uint32_t ri = run_begin; ri < run_end; ++ri) {
+      const uint32_t b = S::items + env.sget(ord + ri) * S::ITEM_W;
+      const uint32_t p = gmx_min_occ_pos(ix, env.sget(b), env.sget(b + 1));
+      m = p < m ? p : m;
+    }
+    where->pos = m;
   }
   // --- loci of the class (union) + per-base hull ---
   uint32_t n_loci = 0, n_hull = 0;

@@ -328,8 +328,10 @@ __device__ uint32_t gmx_tail_item(const GmxIndexView &ix, const BatchView &b, co
   env.status = GMX_TASK_MAPPED;
   env.log_at = 0;
   uint32_t drawn_from = 0;
-  gmx_cover_task(ix, env, finals, nf, len, b.seeds[task >> 1], acc.rng_mode, &drawn_from);
+  GmxWhere where{0u, 0u, o.positions != nullptr};
+  gmx_cover_task(ix, env, finals, nf, len, b.seeds[task >> 1], acc.rng_mode, &drawn_from, &where);
   env.log_abandon();
+  if (o.positions && env.status == GMX_TASK_MAPPED) gmx_position_put(o, task, where.pos, where.n);
   if (env.status == GMX_TASK_MAPPED && is_search) {
     atomicAdd(&acc.stats[4], 1ull);  // exact_mapped
     if (o.outcomes) gmx_outcome_put(o, task, GMX_OUTCOME_MAPPED);
@@ -459,8 +461,10 @@ __global__ void __launch_bounds__(GMX_BLOCK) gmx_cover_kernel(GmxIndexView ix, B
     atomicAdd(&gmx_cover_stats[LIST * 16 + 7], 1ull);
 #endif
     uint32_t drawn_from = 0;
-    gmx_cover_task(ix, env, finals, nf, len, b.seeds[read], acc.rng_mode, &drawn_from);
+    GmxWhere where{0u, 0u, o.positions != nullptr};
+    gmx_cover_task(ix, env, finals, nf, len, b.seeds[read], acc.rng_mode, &drawn_from, &where);
     env.log_abandon();
+    if (o.positions && env.status == GMX_TASK_MAPPED) gmx_position_put(o, task, where.pos, where.n);
     if (o.outcomes && env.status == GMX_TASK_MAPPED && drawn_from > 1u) gmx_outcome_multi(o, task);
 #ifdef GMX_LOOP_STATS
     env.prof(5);
@@ -535,6 +539,7 @@ __global__ void __launch_bounds__(GMX_ONE_THREADS) gmx_cover_one_kernel(GmxIndex
         env.log_at = 0;
         const uint32_t len = read_len(b, ts.task >> 1);
         if (!taken) taken = gmx_cover_single_nested_wide(ix, env, st, len);
+        if (o.positions && taken && env.status == GMX_TASK_MAPPED) gmx_position_put(o, ts.task, gmx_occ_pos(ix, st.hi, st.lo), 1u);  // (its one instance)
         if (env.status == GMX_TASK_LOGFULL) {
           o.log_retry_list[atomicAdd(&o.counters[GMX_CNT_LOG_RETRY * GMX_CNT_STRIDE], 1u)] = entry;
         } else if (env.status != GMX_TASK_MAPPED && atomicCAS(&o.error[0], 0u, env.status) == 0u) {
@@ -584,6 +589,26 @@ constexpr uint32_t gmx_coop_lds_words() {  // + per group: the drawn item's trav
          4u * 3u * CoopSizes<LIST>::Item::P_MAX;
 }
 
+// The position record of a cooperative task: the smallest PRG position among the candidate lanes' occurrences lo .. hi (hi: the text
+// mark for a position), reduced over the group of 16, and n, the sum of the lanes' shares; the group's first lane stores them. Every
+// lane of the wave calls it.
+__device__ __noinline__ void gmx_coop_position(const uint32_t *sa, uint2 *positions, unsigned long long base, uint32_t task, bool candidate,
+                                               uint32_t lo, uint32_t hi, uint32_t n, bool writer) {
+  uint32_t mn = 0xFFFFFFFFu;
+  if (candidate)
+    for (uint32_t i = lo;; ++i) {
+      mn = min(mn, hi == GMX_TEXT_MARK ? i : sa[i]);
+      if (hi == GMX_TEXT_MARK || i == hi) break;
+    }
+#pragma unroll
+  for (uint32_t d = 8; d > 0; d >>= 1) {
+    const uint32_t n2 = __shfl_xor(n, d, 16);
+    n = n + n2 < n ? 0xFFFFFFFFu : n + n2;  // (saturating)
+    mn = min(mn, (uint32_t)__shfl_xor(mn, d, 16));
+  }
+  if (writer) positions[(base << 1) + task] = make_uint2(mn, n);
+}
+
 template <int LIST>
 __global__ void __launch_bounds__(64) gmx_cover_coop_kernel(GmxIndexView ix, BatchView b, SearchOut o, BigOut g, CoverAcc acc) {
   typedef typename CoopSizes<LIST>::Item CoopItemEnv;
@@ -631,9 +656,12 @@ __global__ void __launch_bounds__(64) gmx_cover_coop_kernel(GmxIndexView ix, Bat
     // --- units ---
     GmxFinalState st{0u, 0u, GMX_NIL, GMX_NIL};
     uint32_t w = 0;
+    if (o.positions) ie.sset(SI::hull(ie), 0u);  // (an item lane's hull words are idle — the class scratch holds the hull —: the
+    // lane's share of the position record's n, the number of instances of its final state, waits there for gmx_coop_position)
     if (have && !rejected && gl < ts.nf) {
       st = ts.finals[gl];
       w = (st.traversed != GMX_NIL || st.traversing != GMX_NIL || gmx_text_form(st.hi)) ? 1u : min(st.hi - st.lo, 16u) + 1u;
+      if (o.positions) ie.sset(SI::hull(ie), gmx_text_form(st.hi) ? 1u : st.hi - st.lo + 1u);
     }
     uint32_t incl = w;
 #pragma unroll
@@ -675,6 +703,10 @@ __global__ void __launch_bounds__(64) gmx_cover_coop_kernel(GmxIndexView ix, Bat
         const GmxNode &nd = ix.nodes[ix.pos_node[gmx_occ_pos(ix, f_hi, i)]];
         if (nd.site == 0) {
           nonvar = true;
+          if (o.positions) {  // (its scratch column is free: the occurrence waits there for the position record, like an item's)
+            ie.sset(SI::items + 0, i);
+            ie.sset(SI::items + 1, gmx_text_form(f_hi) ? f_hi : i);
+          }
         } else {
           is_item = true;
           i_lo = i;
@@ -742,6 +774,14 @@ __global__ void __launch_bounds__(64) gmx_cover_coop_kernel(GmxIndexView ix, Bat
       }
     }
     const uint32_t members16 = (uint32_t)(__ballot(member) >> gbase) & 0xFFFFu;
+    // --- the task's position record (SearchOut::positions) ---
+    // Written HERE, before the class is merged and recorded — a task that the next phase turns away (class scratch exceeded: the
+    // serial instance; log full: the replay) is redone from the same states with the same seed and writes the same record again —
+    // from what the lanes left in LDS, and out of line: the kernel's register count, which decides its occupancy, stays what it is
+    // without the recording. Candidates: the drawn class's lanes, or the non-variant lanes (the lump is drawn, or no class at all).
+    if (o.positions)  // (wave-uniform: every lane takes part in the shuffles)
+      gmx_coop_position(ix.sa, o.positions, o.position_base, ts.task, members16 != 0u ? member : nonvar, ie.sget(SI::items + 0),
+                        ie.sget(SI::items + 1), ie.sget(SI::hull(ie)), have && gl == 0 && !rejected && !failed && err == 0u);
     GMX_COOP_PHASE(2);
     // --- the drawn class: its first lane merges the members and records ---
     bool class_overflow = false, class_logfull = false;

@@ -91,7 +91,7 @@ __global__ void gmx_debug_items_kernel(GmxIndexView ix, const GmxFinalState *fin
         it[0] = lo, it[1] = hi, it[2] = tvd, it[3] = tvg, it[4] = es, it[5] = (uint32_t)ea;
         return true;
       },
-      [&](uint32_t i) {
+      [&](uint32_t i, uint32_t) {
         if (n_nonvar < cap_items) nonvar[n_nonvar] = i;
         ++n_nonvar;
       });

@@ -127,6 +127,12 @@ struct gmx_engine {
   uint32_t *d_outcomes = nullptr;
   uint64_t outcome_cap = 0, outcome_count = 0;  // bytes (a multiple of 4) | reads recorded
   uint64_t outcome_epoch = 0;                   // resets so far (gmx_group: is its ledger of ranges still about this buffer?)
+  // Per-read positions (gmx_engine_record_positions; SearchOut::positions): 16 bytes per read handed over since the
+  // last reset — [pos, n] of the forward task, [pos, n] of the reverse-complement one — kept like the outcome bytes: the ENGINE's
+  // buffer whichever workspace runs the launch, zero from position_count on, emptied by the resets (which count outcome_epoch).
+  bool record_positions = false;
+  uint32_t *d_positions = nullptr;
+  uint64_t position_cap = 0, position_count = 0;  // reads
   hipStream_t main_stream = nullptr;  // the twin's main chain (the engine's own: the NULL stream, or the caller's)
   uint32_t twin_toggle = 0;
   hipEvent_t ev_zeroed = nullptr, ev_twin_done = nullptr;  // a queued reset has executed | the twin's last batch has ended
@@ -389,6 +395,27 @@ static int ensure_outcome_capacity(gmx_engine *own, uint64_t n_more) {
   return GMX_OK;
 }
 
+// the same for the position records (four words per read)
+static int ensure_position_capacity(gmx_engine *own, uint64_t n_more) {
+  const uint64_t need = own->position_count + n_more;
+  if (need <= own->position_cap) return GMX_OK;
+  const uint64_t cap = std::max<uint64_t>(need + need / 2, 1u << 16);
+  uint32_t *q = nullptr;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMalloc((void **)&q, cap * 16));
+  hipError_t err = hipMemset(q, 0, cap * 16);
+  if (err == hipSuccess && own->position_count)
+    err = hipMemcpy(q, own->d_positions, own->position_count * 16, hipMemcpyDeviceToDevice);
+  if (err != hipSuccess) {
+    (void)hipFree(q);
+    HIP_TRY(err);
+  }
+  if (own->d_positions) (void)hipFree(own->d_positions);
+  own->d_positions = q;
+  own->position_cap = cap;
+  return GMX_OK;
+}
+
 // launching: called for a launch of n_reads reads that is about to be enqueued (the reserve calls size the workspace only)
 static int ensure_batch_capacity(gmx_engine *e, uint64_t n_reads, bool launching = false) {
   if (launching) {
@@ -396,6 +423,10 @@ static int ensure_batch_capacity(gmx_engine *e, uint64_t n_reads, bool launching
     if (own->record_outcomes) {
       const int orc = ensure_outcome_capacity(own, n_reads);
       if (orc) return orc;
+    }
+    if (own->record_positions) {
+      const int prc = ensure_position_capacity(own, n_reads);
+      if (prc) return prc;
     }
   }
   if (n_reads <= e->cap_reads) return GMX_OK;
@@ -492,6 +523,7 @@ int gmx_engine_create(const gmx_index *ixh, const gmx_engine_opts *opts_in, gmx_
   gmx_engine *e = *out;
   // MEASUREMENT HOOK ONLY (profiles/read_outcomes: the cost of recording in an unchanged benchmark): nothing reads the bytes back
   if (const char *ro = getenv("GMX_RECORD_OUTCOMES")) e->record_outcomes = atoi(ro) != 0;
+  if (const char *rp = getenv("GMX_RECORD_POSITIONS")) e->record_positions = atoi(rp) != 0;  // (the same kind: profiles/read_positions)
   // the twin (a second batch in flight; gmx_engine::twin): nested PRGs and indexes of 2 GB and more
   const gmx::HostIndex &h = gmx_index_host(ixh);
   const bool can = !e->log_sites && e->shared_index && !getenv("GMX_NO_INDEX_SHARE");  // (the twin reads the engine's copy of the index, never one of its own)
@@ -841,6 +873,7 @@ void gmx_engine_destroy(gmx_engine *e) try {
   }
   for (void *p : e->allocs) (void)hipFree(p);
   if (e->d_outcomes) (void)hipFree(e->d_outcomes);
+  if (e->d_positions) (void)hipFree(e->d_positions);
   gmx_dev_index_release(e->shared_index);
   delete e;
 } GMX_GUARD_VOID("gmx_engine_destroy")
@@ -859,6 +892,8 @@ int gmx_engine_reset(gmx_engine *e) try {
   }
   if (e->outcome_count) HIP_TRY(hipMemset(e->d_outcomes, 0, (e->outcome_count + 3) & ~3ull));
   e->outcome_count = 0;
+  if (e->position_count) HIP_TRY(hipMemset(e->d_positions, 0, e->position_count * 16));
+  e->position_count = 0;
   ++e->outcome_epoch;
   e->log_counts.clear();
   e->log_known = e->log_reads_since = 0;
@@ -878,6 +913,8 @@ int gmx_engine_reset_async(gmx_engine *e, void *hip_stream) try {
   //  for the accumulators' zeroing, queued on this stream later; the count restarts with the next launch)
   if (e->outcome_count) HIP_TRY(hipMemsetAsync(e->d_outcomes, 0, (e->outcome_count + 3) & ~3ull, st));
   e->outcome_count = 0;
+  if (e->position_count) HIP_TRY(hipMemsetAsync(e->d_positions, 0, e->position_count * 16, st));  // (the position records with them)
+  e->position_count = 0;
   ++e->outcome_epoch;
   e->reset_pending = true;
   e->reset_stream = st;
@@ -1127,6 +1164,11 @@ static int launch_batch(gmx_engine *e, const BatchInput &in, hipStream_t stream)
       o.outcomes = own->d_outcomes;
       o.outcome_base = own->outcome_count;
       own->outcome_count += n_reads;
+    }
+    if (own->record_positions) {
+      o.positions = reinterpret_cast<uint2 *>(own->d_positions);
+      o.position_base = own->position_count;
+      own->position_count += n_reads;
     }
   }
   uint32_t n_tasks = (uint32_t)n_reads * 2;
@@ -2250,6 +2292,44 @@ static uint64_t emit_log_counts(const gmx_engine *e, LogForm which, uint32_t *ou
   }
   return n;
 }
+
+int gmx_engine_record_positions(gmx_engine *e, int on) try {
+  if (!e) {
+    gmx_set_error("null engine");
+    return GMX_EINVAL;
+  }
+  e->record_positions = on != 0;
+  return GMX_OK;
+} GMX_GUARD_INT("gmx_engine_record_positions")
+
+int64_t gmx_engine_position_count(gmx_engine *e) try {
+  if (!e) {
+    gmx_set_error("null engine");
+    return GMX_EINVAL;
+  }
+  return (int64_t)e->position_count;
+} GMX_GUARD_INT("gmx_engine_position_count")
+
+int gmx_engine_fetch_positions(gmx_engine *e, uint64_t first, uint64_t n, uint32_t *out) try {
+  if (!e || (n && !out)) {
+    gmx_set_error("gmx_engine_fetch_positions: null argument");
+    return GMX_EINVAL;
+  }
+  if (first > e->position_count || n > e->position_count - first) {
+    gmx_set_error("gmx_engine_fetch_positions: reads " + std::to_string(first) + " .. " + std::to_string(first + n) + " of " +
+                  std::to_string(e->position_count) + " recorded");
+    return GMX_EINVAL;
+  }
+  {
+    int frc = flush_reset(e);
+    if (frc) return frc;
+    if ((frc = log_settle(e))) return frc;  // (a task redone after a full log leaves its record then)
+  }
+  HIP_TRY(hipSetDevice(e->opts.device));
+  HIP_TRY(hipDeviceSynchronize());  // both workspaces' streams
+  if (n) HIP_TRY(hipMemcpy(out, e->d_positions + 4 * first, n * 16, hipMemcpyDeviceToHost));
+  return GMX_OK;
+} GMX_GUARD_INT("gmx_engine_fetch_positions")
 
 int64_t gmx_coverage_fetch_grouped_log(gmx_engine *e, uint32_t *out, uint64_t cap_words) try {
   if (!e) return GMX_EINVAL;

@@ -1033,6 +1033,13 @@ struct SearchOut {
   // code is 0: nothing to write) — so a task redone in a larger tier leaves one code, like one count.
   uint32_t *outcomes;
   unsigned long long outcome_base;
+  // Per-read positions (gmx_engine_record_positions; null: not recorded — one uniform branch per site). Eight bytes
+  // per task, task t of this launch at positions[2 * position_base + t]: .x the PRG position of the read's first base, the
+  // smallest among the instances the selection chose from, .y the number of mapping instances. Written by the routine that
+  // RECORDS the task's coverage (or, for a compact record, by finish_lane), once it is known to have succeeded: a task redone
+  // in a larger tier or after a full log writes then, the same value whichever route; an unmapped task writes nothing.
+  uint2 *positions;
+  unsigned long long position_base;
 };
 // (the task codes: GMX_OUTCOME_* of include/gmx.h)
 #define GMX_OUTCOME_MULTI 16u  // (the forward task's bit; << 1: the reverse-complement task's)
@@ -1047,6 +1054,10 @@ __device__ __forceinline__ void gmx_outcome_put(const SearchOut &o, uint32_t tas
 }
 __device__ __forceinline__ void gmx_outcome_multi(const SearchOut &o, uint32_t task) {
   gmx_outcome_or(o, task, GMX_OUTCOME_MULTI << (task & 1u));
+}
+// a task's position record: its own eight bytes, one plain 64-bit store (no other task shares them: no atomic)
+__device__ __forceinline__ void gmx_position_put(const SearchOut &o, uint32_t task, uint32_t pos, uint32_t n) {
+  o.positions[(o.position_base << 1) + task] = make_uint2(pos, n);
 }
 
 #ifndef GMX_REGIONS
@@ -1167,6 +1178,7 @@ __device__ __forceinline__ void finish_lane(const GmxIndexView &ix, const Search
   enum : uint32_t { Q_OVER = GMX_REGIONS, Q_ALIVE, Q_DEAD, Q_GENERAL, Q_N, Q_SKIPPED = Q_N, Q_COLS };  // Q_SKIPPED: a count only
   const uint32_t cat = mapped ? (compact ? region : Q_GENERAL) : over ? Q_OVER : alive ? Q_ALIVE : dead ? Q_DEAD : 0xFFu;
   if (o.outcomes && mapped) gmx_outcome_put(o, task, GMX_OUTCOME_MAPPED);  // (counted into stats[4] below)
+  if (o.positions && compact) gmx_position_put(o, task, ctx.first_pos, 1u);  // (one text-form state: its one instance; the others: their coverage routine)
   __shared__ uint32_t q_cnt[GMX_BLOCK / 64][Q_COLS];
   __shared__ uint32_t q_base[Q_N];
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

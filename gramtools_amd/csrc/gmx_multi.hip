@@ -265,6 +265,10 @@ struct gmx_group {
   struct OutcomeRange { uint64_t first, count; size_t member; uint64_t member_first; };
   std::vector<OutcomeRange> ranges;
   uint64_t n_outcomes = 0, epochs = 0;
+  // (the position records, gmx_engine_record_positions: the same ledger over the members' position counts — the two recordings
+  //  are switched independently, so a range of one need not be a range of the other)
+  std::vector<OutcomeRange> pos_ranges;
+  uint64_t n_positions = 0;
 };
 static uint64_t group_epochs(const gmx_group *g) {
   uint64_t s = 0;
@@ -276,14 +280,18 @@ static void group_ledger_sync(gmx_group *g) {  // a member was reset: the ranges
   if (now != g->epochs) {
     g->ranges.clear();
     g->n_outcomes = 0;
+    g->pos_ranges.clear();
+    g->n_positions = 0;
     g->epochs = now;
   }
 }
 // around a feed: what every member's count was before it, and the ranges the members recorded (member order = read order)
+// (entries [0, n): the outcome counts, [n, 2 n): the position counts)
 static std::vector<uint64_t> group_counts(gmx_group *g) {
   group_ledger_sync(g);
   std::vector<uint64_t> c;
   for (auto const &m : g->ms) c.push_back((uint64_t)std::max<int64_t>(gmx_engine_outcome_count(m.e), 0));
+  for (auto const &m : g->ms) c.push_back((uint64_t)std::max<int64_t>(gmx_engine_position_count(m.e), 0));
   return c;
 }
 static void group_note(gmx_group *g, const std::vector<uint64_t> &before) {
@@ -292,6 +300,13 @@ static void group_note(gmx_group *g, const std::vector<uint64_t> &before) {
     if (now <= before[i]) continue;
     g->ranges.push_back({g->n_outcomes, now - before[i], i, before[i]});
     g->n_outcomes += now - before[i];
+  }
+  const size_t n = g->ms.size();
+  for (size_t i = 0; i < n; ++i) {
+    const uint64_t now = (uint64_t)std::max<int64_t>(gmx_engine_position_count(g->ms[i].e), 0);
+    if (now <= before[n + i]) continue;
+    g->pos_ranges.push_back({g->n_positions, now - before[n + i], i, before[n + i]});
+    g->n_positions += now - before[n + i];
   }
 }
 
@@ -525,6 +540,47 @@ int gmx_group_fetch_outcomes(gmx_group *g, uint64_t first, uint64_t n, uint8_t *
   }
   return GMX_OK;
 } GMX_GUARD_INT("gmx_group_fetch_outcomes")
+
+int gmx_group_record_positions(gmx_group *g, int on) try {
+  if (!g) {
+    gmx_set_error("null group");
+    return GMX_EINVAL;
+  }
+  for (auto const &m : g->ms) {
+    const int rc = gmx_engine_record_positions(m.e, on);
+    if (rc) return rc;
+  }
+  return GMX_OK;
+} GMX_GUARD_INT("gmx_group_record_positions")
+
+int64_t gmx_group_position_count(gmx_group *g) try {
+  if (!g) {
+    gmx_set_error("null group");
+    return GMX_EINVAL;
+  }
+  group_ledger_sync(g);
+  return (int64_t)g->n_positions;
+} GMX_GUARD_INT("gmx_group_position_count")
+
+int gmx_group_fetch_positions(gmx_group *g, uint64_t first, uint64_t n, uint32_t *out) try {
+  if (!g || (n && !out)) {
+    gmx_set_error("gmx_group_fetch_positions: null argument");
+    return GMX_EINVAL;
+  }
+  group_ledger_sync(g);
+  if (first > g->n_positions || n > g->n_positions - first) {
+    gmx_set_error("gmx_group_fetch_positions: reads " + std::to_string(first) + " .. " + std::to_string(first + n) + " of " +
+                  std::to_string(g->n_positions) + " recorded");
+    return GMX_EINVAL;
+  }
+  for (auto const &r : g->pos_ranges) {  // (the exchange is not involved: every member holds its own reads' records)
+    const uint64_t lo = std::max(first, r.first), hi = std::min(first + n, r.first + r.count);
+    if (lo >= hi) continue;
+    const int rc = gmx_engine_fetch_positions(g->ms[r.member].e, r.member_first + (lo - r.first), hi - lo, out + 4 * (lo - first));
+    if (rc) return rc;
+  }
+  return GMX_OK;
+} GMX_GUARD_INT("gmx_group_fetch_positions")
 
 int gmx_group_sync_uploads(gmx_group *g) try {
   if (!g) {

@@ -80,6 +80,12 @@ const char *kGenotypeHelp =
     "                              reverse complement (0 skipped, 1 a k-mer not in the index, 2 no exact mapping, 3 exactly\n"
     "                              mapped), bits 4 / 5 that orientation had several mapping instances to draw from — and\n"
     "                              read_outcomes.json, the count of every byte value\n"
+    "  --read_positions            where every read mapped (engine extension): writes genotype_dir/read_positions.bin — a\n"
+    "                              16-byte header (\"GMXP\", uint32 version 1, uint64 read count, little-endian), then four\n"
+    "                              uint32 per read in the order of the reads files: pos and n of the read as given, pos and n\n"
+    "                              of its reverse complement (n: its number of mapping instances, 0 when not exactly mapped;\n"
+    "                              pos: 0-based index into the linearised PRG of its first base, the smallest among the\n"
+    "                              instances the selection chose from) — and read_positions.json, counts and a histogram of n\n"
     "  --strand_coverage           coverage per strand (engine extension): writes, beside the three coverage files,\n"
     "                              coverage/allele_sum_coverage.forward and .reverse and\n"
     "                              coverage/allele_base_coverage.forward.json and .reverse.json — what the reads as given and\n"
@@ -2212,6 +2218,10 @@ int run_genotype(const Args &a) {
   std::vector<OutcomeSeg> outcome_segs;
   if (read_outcomes)
     for (int d = 0; d < gmx_group_size(grp); ++d) GMX_CHECK(gmx_engine_record_outcomes(gmx_group_engine(grp, d), 1));
+  // --read_positions: the same bookkeeping for the engines' position records (their counts are the engines' own)
+  const bool read_positions = a.has("read_positions");
+  std::vector<OutcomeSeg> position_segs;
+  if (read_positions) GMX_CHECK(gmx_group_record_positions(grp, 1));
   // --strand_coverage: every engine keeps the reads' and their reverse complements' coverage apart, across samples (a reset
   // zeroes both blocks); the exchange carries both
   const bool strand_coverage = a.has("strand_coverage");
@@ -2219,10 +2229,17 @@ int run_genotype(const Args &a) {
   const bool strand_bias = a.has("strand_bias");
   if (strand_coverage || strand_bias) GMX_CHECK(gmx_group_record_strands(grp, 1));
   auto note_outcomes = [&](int engine, uint64_t n) {  // BEFORE the call that hands n reads to `engine` (or to the group)
-    if (!read_outcomes || n == 0) return;
-    const int64_t at = engine < 0 ? gmx_group_outcome_count(grp) : gmx_engine_outcome_count(gmx_group_engine(grp, engine));
-    if (at < 0) die(std::string("gram: read outcomes: ") + gmx_last_error());
-    outcome_segs.push_back(OutcomeSeg{engine, (uint64_t)at, n});
+    if (n == 0) return;
+    if (read_outcomes) {
+      const int64_t at = engine < 0 ? gmx_group_outcome_count(grp) : gmx_engine_outcome_count(gmx_group_engine(grp, engine));
+      if (at < 0) die(std::string("gram: read outcomes: ") + gmx_last_error());
+      outcome_segs.push_back(OutcomeSeg{engine, (uint64_t)at, n});
+    }
+    if (read_positions) {
+      const int64_t at = engine < 0 ? gmx_group_position_count(grp) : gmx_engine_position_count(gmx_group_engine(grp, engine));
+      if (at < 0) die(std::string("gram: read positions: ") + gmx_last_error());
+      position_segs.push_back(OutcomeSeg{engine, (uint64_t)at, n});
+    }
   };
   // workspace for the calls the feed will make (a block of a reads file per call, at most 1 M reads per engine)
   for (int d = 0; d < gmx_group_size(grp); ++d) GMX_CHECK(gmx_engine_reserve_packed(gmx_group_engine(grp, d), info.is_nested ? 4u << 20 : 3u << 19 /* (a decoded BGZF chunk of 150 bp reads: 1.46 M) */, ((info.is_nested ? 24ull : 6ull) << 20) + 64));
@@ -2248,6 +2265,7 @@ int run_genotype(const Args &a) {
   if (sample_i > 0) {  // the accumulators and read counters of the sample before
     for (int d = 0; d < gmx_group_size(grp); ++d) GMX_CHECK(gmx_engine_reset(gmx_group_engine(grp, d)));
     outcome_segs.clear();
+    position_segs.clear();
     g_feed = FeedTimes{};
   }
   std::cout << "Running quasimap" << std::endl;
@@ -2503,6 +2521,44 @@ int run_genotype(const Args &a) {
         first_value = false;
       }
     o << "}}\n";
+    close_checked(o, json_path);
+  }
+  if (read_positions) {  // G/read_positions.bin + .json: the engines' records put together in the order of the reads files
+    std::vector<uint32_t> words(4 * std::max<uint64_t>(total_reads, 1));
+    uint64_t at = 0;
+    for (auto const &sg : position_segs) {
+      if (at + sg.n > total_reads) die("gram: read positions: more records than reads");
+      if (sg.engine < 0)
+        GMX_CHECK(gmx_group_fetch_positions(grp, sg.first, sg.n, words.data() + 4 * at));
+      else
+        GMX_CHECK(gmx_engine_fetch_positions(gmx_group_engine(grp, sg.engine), sg.first, sg.n, words.data() + 4 * at));
+      at += sg.n;
+    }
+    if (at != total_reads) die("gram: read positions: " + std::to_string(at) + " records for " + std::to_string(total_reads) + " reads");
+    const std::string bin_path = join(run_dir, "read_positions.bin"), json_path = join(run_dir, "read_positions.json");
+    {
+      std::ofstream o(bin_path, std::ios::binary);
+      unsigned char header[16] = {'G', 'M', 'X', 'P', 1, 0, 0, 0};
+      for (int i = 0; i < 8; ++i) header[8 + i] = (unsigned char)((total_reads >> (8 * i)) & 0xFF);
+      o.write(reinterpret_cast<const char *>(header), 16);
+      std::vector<unsigned char> le(16 * std::max<uint64_t>(total_reads, 1));  // (little-endian whatever the host)
+      for (uint64_t i = 0; i < 4 * total_reads; ++i)
+        for (int k = 0; k < 4; ++k) le[4 * i + k] = (unsigned char)((words[i] >> (8 * k)) & 0xFF);
+      o.write(reinterpret_cast<const char *>(le.data()), (std::streamsize)(16 * total_reads));
+      close_checked(o, bin_path);
+    }
+    uint64_t mapped = 0, unique = 0, multi = 0, hist[5] = {0};  // n: 1 | 2 | 3-10 | 11-100 | above 100
+    for (uint64_t t = 0; t < 2 * total_reads; ++t) {
+      const uint32_t n = words[2 * t + 1];
+      if (n == 0) continue;
+      ++mapped;
+      ++(n == 1 ? unique : multi);
+      ++hist[n == 1 ? 0 : n == 2 ? 1 : n <= 10 ? 2 : n <= 100 ? 3 : 4];
+    }
+    std::ofstream o(json_path);
+    o << "{\"reads\":" << total_reads << ",\"tasks_mapped\":" << mapped << ",\"tasks_one_instance\":" << unique
+      << ",\"tasks_several_instances\":" << multi << ",\"instances_histogram\":{\"1\":" << hist[0] << ",\"2\":" << hist[1]
+      << ",\"3-10\":" << hist[2] << ",\"11-100\":" << hist[3] << ",\"above_100\":" << hist[4] << "}}\n";
     close_checked(o, json_path);
   }
   std::string rs_path = join(run_dir, "read_stats.json");

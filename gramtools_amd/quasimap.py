@@ -576,6 +576,28 @@ class Quasimapper:
         recorded are kept apart; see coverage(strand=...). Only while nothing is recorded: after creation or reset()."""
         check(self.lib.gmx_engine_record_strands(self.h, 1 if on else 0))
 
+    def record_positions(self, on: bool = True):
+        """From the next mapping call on every read leaves a position record (gmx_engine_record_positions); see positions()."""
+        check(self.lib.gmx_engine_record_positions(self.h, 1 if on else 0))
+
+    def position_count(self) -> int:
+        """Reads with a position record since the last reset."""
+        return check(self.lib.gmx_engine_position_count(self.h))
+
+    def positions(self, first: int = 0, n: int = None) -> np.ndarray:
+        """The position records of reads first .. first + n (default: all recorded), in the order the reads were handed over:
+        an (n, 4) uint32 array [pos_fwd, n_fwd, pos_rc, n_rc] — n the number of mapping instances of the orientation (0: not
+        exactly mapped), pos the 0-based index into the linearised PRG of the read's first base, the smallest among the
+        instances the selection chose from (gmx_engine_fetch_positions)."""
+        count = self.position_count()
+        if n is None:
+            n = count - first
+        if first < 0 or n < 0 or first + n > count:
+            raise ValueError(f"positions: reads {first} .. {first + n} of {count} recorded")
+        out = np.zeros((max(n, 1), 4), dtype=np.uint32)
+        check(self.lib.gmx_engine_fetch_positions(self.h, first, n, _p(out, C.c_uint32)))
+        return out[:n]
+
     def enable_timing(self, on=True):
         check(self.lib.gmx_engine_enable_timing(self.h, 1 if on else 0))
 
@@ -966,6 +988,24 @@ class QuasimapperGroup:
         view = Quasimapper.__new__(Quasimapper)
         view.lib, view.index, view.h = self.lib, self.index, C.c_void_p(self.lib.gmx_group_engine(self.h, member))
         return view
+
+    def record_positions(self, on: bool = True):
+        """Per-read positions on every member (Quasimapper.record_positions); see positions()."""
+        check(self.lib.gmx_group_record_positions(self.h, 1 if on else 0))
+
+    def position_count(self) -> int:
+        return check(self.lib.gmx_group_position_count(self.h))
+
+    def positions(self, first: int = 0, n: int = None) -> np.ndarray:
+        """Position records of the reads handed to the group's feeds, in that order (gmx_group_fetch_positions)."""
+        count = self.position_count()
+        if n is None:
+            n = count - first
+        if first < 0 or n < 0 or first + n > count:
+            raise ValueError(f"positions: reads {first} .. {first + n} of {count} recorded")
+        out = np.zeros((max(n, 1), 4), dtype=np.uint32)
+        check(self.lib.gmx_group_fetch_positions(self.h, first, n, _p(out, C.c_uint32)))
+        return out[:n]
 
     def coverage(self, member: int = 0, strand=None) -> Coverage:
         """Coverage held by engine `member` (after :meth:`allreduce`: the totals of the whole job, on every member); with

@@ -522,6 +522,22 @@ int gmx_coverage_fetch(gmx_engine *e, uint32_t *allele_sum, uint32_t *per_base, 
 int gmx_engine_record_outcomes(gmx_engine *e, int on);
 int64_t gmx_engine_outcome_count(gmx_engine *e);
 int gmx_engine_fetch_outcomes(gmx_engine *e, uint64_t first, uint64_t n, uint8_t *out);
+
+/* Per-read positions: where every read mapped and how many places it could have mapped to (off by default; nothing changes
+ * while it is off). Four little-endian uint32 per read: [pos_fwd, n_fwd, pos_rc, n_rc], the read as given and its reverse
+ * complement (zero when the engine maps forward only).
+ *   n    the number of mapping instances of an exactly mapped task: one per suffix-array index of each of its final search
+ *        states (two states at one text position on different allele paths count as two); saturates at 0xFFFFFFFF.
+ *        n == 0: the task is not exactly mapped, and pos is 0.
+ *   pos  0-based index into the linearised PRG (the integer vector the index was built from: the coordinate of
+ *        gmx_index_copy_sa and of the rows of gmx_index_copy_pos_info) of the first base of the oriented read — the SMALLEST
+ *        such position among the instances the selection chose from: all of them when the task has no variant-site class,
+ *        the instances outside every site when the seeded draw fell on them, else the instances of the drawn class. The
+ *        minimum makes the record independent of the order in which the engine's tiers find the states.
+ * Buffer, order, resets and the fetch are those of the outcome bytes above; the two recordings are independent. */
+int gmx_engine_record_positions(gmx_engine *e, int on);
+int64_t gmx_engine_position_count(gmx_engine *e);
+int gmx_engine_fetch_positions(gmx_engine *e, uint64_t first, uint64_t n, uint32_t *out);
 /* Coverage per strand (off by default; nothing changes while it is off). Every read is mapped as given and reverse-complemented;
  * with recording on, the engine keeps TWO accumulator blocks — what the reads as given added, and what their reverse complements
  * added — instead of one: allele-sum, dense grouped counts and per-base counts of every site, each per strand. The read counters
@@ -670,6 +686,11 @@ int gmx_group_allreduce(gmx_group *g); /* the exchange; synchronises every engin
  * gmx_group_map_reads_* since the members' last reset. The exchange is not involved. */
 int64_t gmx_group_outcome_count(gmx_group *g);
 int gmx_group_fetch_outcomes(gmx_group *g, uint64_t first, uint64_t n, uint8_t *out);
+/* The same for the position records (gmx_engine_record_positions; four words per read); gmx_group_record_positions switches
+ * every member. */
+int gmx_group_record_positions(gmx_group *g, int on);
+int64_t gmx_group_position_count(gmx_group *g);
+int gmx_group_fetch_positions(gmx_group *g, uint64_t first, uint64_t n, uint32_t *out);
 /* Coverage per strand on every member (gmx_engine_record_strands; the same rule: while no member has recorded anything). All
  * members or none: when one cannot be switched, those before it go back. After gmx_group_allreduce every member's two blocks
  * hold the whole job's per-strand totals. */
