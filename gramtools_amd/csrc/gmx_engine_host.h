@@ -18,6 +18,57 @@
 enum : int { GMX_TK_SEED = 0, GMX_TK_FILTER0, GMX_TK_FILTER1, GMX_TK_SINGLE, GMX_TK_EXTEND2, GMX_TK_UNPACK, GMX_TK_N };
 static_assert(GMX_TK_N <= GMX_TIMED_KERNELS, "gmx_timing::kernel_ms holds GMX_TIMED_KERNELS entries");
 
+// A per-read log: `stride` bytes per read handed over since the last reset, appended launch by launch to one device
+// buffer. Bytes from the recorded prefix on are zero (the kernels OR into zeroed words); the buffer is not an entry of
+// gmx_engine::allocs: a growing one replaces it. Only reserve, clear, claim and release change d, cap and count.
+struct GmxReadLog {
+  const uint32_t stride;  // bytes per read
+  bool on = false;
+  uint32_t *d = nullptr;
+  uint64_t cap = 0, count = 0;  // bytes (a multiple of 4) | reads recorded
+
+  // the recorded prefix in bytes, to whole words: launches share the words of a log whose stride is no multiple of 4
+  uint64_t used() const { return (count * stride + 3) & ~3ull; }
+
+  // room for n_more reads (never while one of the engine's kernels is being enqueued: before the batch's first). Growth waits
+  // for the launches in flight — they write the old buffer — and carries their records over.
+  int reserve(uint64_t n_more) {
+    const uint64_t need = (count + n_more) * stride;
+    if (need <= cap) return GMX_OK;
+    const uint64_t grown = (std::max<uint64_t>(need + need / 2, 1u << 20) + 3) & ~3ull;
+    uint32_t *q = nullptr;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMalloc((void **)&q, grown));
+    hipError_t err = hipMemset(q, 0, grown);
+    if (err == hipSuccess && count) err = hipMemcpy(q, d, used(), hipMemcpyDeviceToDevice);
+    if (err != hipSuccess) {
+      (void)hipFree(q);
+      HIP_TRY(err);
+    }
+    release();
+    d = q;
+    cap = grown;
+    return GMX_OK;
+  }
+  // the recorded prefix back to zero — on *stream, behind what that stream holds, or at once (null) — and the count with it
+  int clear(const hipStream_t *stream) {
+    if (count) HIP_TRY(stream ? hipMemsetAsync(d, 0, used(), *stream) : hipMemset(d, 0, used()));
+    count = 0;
+    return GMX_OK;
+  }
+  // a launch of n reads: the index of its first read (room was made by reserve)
+  uint64_t claim(uint64_t n) {
+    const uint64_t base = count;
+    count += n;
+    return base;
+  }
+  void release() {
+    if (d) (void)hipFree(d);
+    d = nullptr;
+    cap = 0;
+  }
+};
+
 struct gmx_engine {
   gmx_engine_opts opts;
   GmxIndexView dview;  // device pointers
@@ -120,19 +171,12 @@ struct gmx_engine {
   gmx_engine *twin = nullptr;
   gmx_engine *owner = nullptr;  // (of a twin: the engine it belongs to)
   bool is_twin = false, twin_off = false;
-  // Per-read outcomes (gmx_engine_record_outcomes; SearchOut::outcomes): one byte per read handed over since the last reset, in the
-  // ENGINE's buffer whichever workspace runs the launch — a launch is given its first read's index when it is enqueued. Bytes
-  // from outcome_count on are zero (the kernels OR into zeroed words); not an entry of `allocs`: a growing buffer replaces it.
-  bool record_outcomes = false;
-  uint32_t *d_outcomes = nullptr;
-  uint64_t outcome_cap = 0, outcome_count = 0;  // bytes (a multiple of 4) | reads recorded
-  uint64_t outcome_epoch = 0;                   // resets so far (gmx_group: is its ledger of ranges still about this buffer?)
-  // Per-read positions (gmx_engine_record_positions; SearchOut::positions): 16 bytes per read handed over since the
-  // last reset — [pos, n] of the forward task, [pos, n] of the reverse-complement one — kept like the outcome bytes: the ENGINE's
-  // buffer whichever workspace runs the launch, zero from position_count on, emptied by the resets (which count outcome_epoch).
-  bool record_positions = false;
-  uint32_t *d_positions = nullptr;
-  uint64_t position_cap = 0, position_count = 0;  // reads
+  // The per-read logs, in the ENGINE's buffers whichever workspace runs the launch — a launch is given its first read's index
+  // when it is enqueued. Outcomes (gmx_engine_record_outcomes; SearchOut::outcomes): one byte per read. Positions
+  // (gmx_engine_record_positions; SearchOut::positions): 16 bytes per read — [pos, n] of the forward task, [pos, n] of
+  // the reverse-complement one.
+  GmxReadLog outcomes{1}, positions{16};
+  uint64_t reset_epoch = 0;  // resets so far (gmx_group: are its ledgers of ranges still about these buffers?)
   hipStream_t main_stream = nullptr;  // the twin's main chain (the engine's own: the NULL stream, or the caller's)
   uint32_t twin_toggle = 0;
   hipEvent_t ev_zeroed = nullptr, ev_twin_done = nullptr;  // a queued reset has executed | the twin's last batch has ended
@@ -373,61 +417,15 @@ void gmx_engine_default_opts(gmx_engine_opts *o) try {
   o->log_cap_words = 0;
 } GMX_GUARD_VOID("gmx_engine_default_opts")
 
-// room for n_more reads' outcome bytes in the engine's buffer (never while one of its kernels is being enqueued: before the
-// batch's first). Growth waits for the launches in flight — they write the old buffer — and carries their bytes over.
-static int ensure_outcome_capacity(gmx_engine *own, uint64_t n_more) {
-  const uint64_t need = own->outcome_count + n_more;
-  if (need <= own->outcome_cap) return GMX_OK;
-  const uint64_t cap = (std::max<uint64_t>(need + need / 2, 1u << 20) + 3) & ~3ull;
-  uint32_t *q = nullptr;
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMalloc((void **)&q, cap));
-  hipError_t err = hipMemset(q, 0, cap);
-  if (err == hipSuccess && own->outcome_count)
-    err = hipMemcpy(q, own->d_outcomes, (own->outcome_count + 3) & ~3ull, hipMemcpyDeviceToDevice);
-  if (err != hipSuccess) {
-    (void)hipFree(q);
-    HIP_TRY(err);
-  }
-  if (own->d_outcomes) (void)hipFree(own->d_outcomes);
-  own->d_outcomes = q;
-  own->outcome_cap = cap;
-  return GMX_OK;
-}
-
-// the same for the position records (four words per read)
-static int ensure_position_capacity(gmx_engine *own, uint64_t n_more) {
-  const uint64_t need = own->position_count + n_more;
-  if (need <= own->position_cap) return GMX_OK;
-  const uint64_t cap = std::max<uint64_t>(need + need / 2, 1u << 16);
-  uint32_t *q = nullptr;
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMalloc((void **)&q, cap * 16));
-  hipError_t err = hipMemset(q, 0, cap * 16);
-  if (err == hipSuccess && own->position_count)
-    err = hipMemcpy(q, own->d_positions, own->position_count * 16, hipMemcpyDeviceToDevice);
-  if (err != hipSuccess) {
-    (void)hipFree(q);
-    HIP_TRY(err);
-  }
-  if (own->d_positions) (void)hipFree(own->d_positions);
-  own->d_positions = q;
-  own->position_cap = cap;
-  return GMX_OK;
-}
-
 // launching: called for a launch of n_reads reads that is about to be enqueued (the reserve calls size the workspace only)
 static int ensure_batch_capacity(gmx_engine *e, uint64_t n_reads, bool launching = false) {
   if (launching) {
     gmx_engine *own = e->owner ? e->owner : e;
-    if (own->record_outcomes) {
-      const int orc = ensure_outcome_capacity(own, n_reads);
-      if (orc) return orc;
-    }
-    if (own->record_positions) {
-      const int prc = ensure_position_capacity(own, n_reads);
-      if (prc) return prc;
-    }
+    for (GmxReadLog *log : {&own->outcomes, &own->positions})
+      if (log->on) {
+        const int lrc = log->reserve(n_reads);
+        if (lrc) return lrc;
+      }
   }
   if (n_reads <= e->cap_reads) return GMX_OK;
   // (re)allocate: old buffers stay in `allocs` until destroy; growth is rare (first call sizes it)
@@ -522,8 +520,8 @@ int gmx_engine_create(const gmx_index *ixh, const gmx_engine_opts *opts_in, gmx_
   if (rc) return rc;
   gmx_engine *e = *out;
   // MEASUREMENT HOOK ONLY (profiles/read_outcomes: the cost of recording in an unchanged benchmark): nothing reads the bytes back
-  if (const char *ro = getenv("GMX_RECORD_OUTCOMES")) e->record_outcomes = atoi(ro) != 0;
-  if (const char *rp = getenv("GMX_RECORD_POSITIONS")) e->record_positions = atoi(rp) != 0;  // (the same kind: profiles/read_positions)
+  if (const char *ro = getenv("GMX_RECORD_OUTCOMES")) e->outcomes.on = atoi(ro) != 0;
+  if (const char *rp = getenv("GMX_RECORD_POSITIONS")) e->positions.on = atoi(rp) != 0;  // (the same kind: profiles/read_positions)
   // the twin (a second batch in flight; gmx_engine::twin): nested PRGs and indexes of 2 GB and more
   const gmx::HostIndex &h = gmx_index_host(ixh);
   const bool can = !e->log_sites && e->shared_index && !getenv("GMX_NO_INDEX_SHARE");  // (the twin reads the engine's copy of the index, never one of its own)
@@ -872,8 +870,8 @@ void gmx_engine_destroy(gmx_engine *e) try {
     if (sl.h_seeds) (void)hipHostFree(sl.h_seeds);
   }
   for (void *p : e->allocs) (void)hipFree(p);
-  if (e->d_outcomes) (void)hipFree(e->d_outcomes);
-  if (e->d_positions) (void)hipFree(e->d_positions);
+  e->outcomes.release();
+  e->positions.release();
   gmx_dev_index_release(e->shared_index);
   delete e;
 } GMX_GUARD_VOID("gmx_engine_destroy")
@@ -890,11 +888,9 @@ int gmx_engine_reset(gmx_engine *e) try {
     HIP_TRY(hipMemset(e->twin->d_counters, 0, GMX_N_COUNTERS * GMX_CNT_STRIDE * 4));
     e->twin_in_flight = false;
   }
-  if (e->outcome_count) HIP_TRY(hipMemset(e->d_outcomes, 0, (e->outcome_count + 3) & ~3ull));
-  e->outcome_count = 0;
-  if (e->position_count) HIP_TRY(hipMemset(e->d_positions, 0, e->position_count * 16));
-  e->position_count = 0;
-  ++e->outcome_epoch;
+  int lrc = e->outcomes.clear(nullptr);
+  if (lrc || (lrc = e->positions.clear(nullptr))) return lrc;
+  ++e->reset_epoch;
   e->log_counts.clear();
   e->log_known = e->log_reads_since = 0;
   e->log_state_pending = false;
@@ -909,13 +905,10 @@ int gmx_engine_reset_async(gmx_engine *e, void *hip_stream) try {
   if (frc) return frc;
   if ((frc = twin_join(e, st))) return frc;  // (the zeroing comes behind whatever the twin still records)
   e->twin_in_flight = false;
-  // (the outcome bytes: zeroed on the reset's stream now — behind the batches before, ahead of the next one, whose twin launch waits
-  //  for the accumulators' zeroing, queued on this stream later; the count restarts with the next launch)
-  if (e->outcome_count) HIP_TRY(hipMemsetAsync(e->d_outcomes, 0, (e->outcome_count + 3) & ~3ull, st));
-  e->outcome_count = 0;
-  if (e->position_count) HIP_TRY(hipMemsetAsync(e->d_positions, 0, e->position_count * 16, st));  // (the position records with them)
-  e->position_count = 0;
-  ++e->outcome_epoch;
+  // (the per-read logs: zeroed on the reset's stream now — behind the batches before, ahead of the next one, whose twin launch waits
+  //  for the accumulators' zeroing, queued on this stream later; the counts restart with the next launch)
+  if ((frc = e->outcomes.clear(&st)) || (frc = e->positions.clear(&st))) return frc;
+  ++e->reset_epoch;
   e->reset_pending = true;
   e->reset_stream = st;
   e->log_counts.clear();  // what earlier batches left in the device log goes with the cursor
@@ -1160,15 +1153,13 @@ static int launch_batch(gmx_engine *e, const BatchInput &in, hipStream_t stream)
   {
     gmx_engine *own = e->owner ? e->owner : e;
     own->recorded = true;
-    if (own->record_outcomes) {  // (room was made in ensure_batch_capacity)
-      o.outcomes = own->d_outcomes;
-      o.outcome_base = own->outcome_count;
-      own->outcome_count += n_reads;
+    if (own->outcomes.on) {  // (room was made in ensure_batch_capacity)
+      o.outcomes = own->outcomes.d;
+      o.outcome_base = own->outcomes.claim(n_reads);
     }
-    if (own->record_positions) {
-      o.positions = reinterpret_cast<uint2 *>(own->d_positions);
-      o.position_base = own->position_count;
-      own->position_count += n_reads;
+    if (own->positions.on) {
+      o.positions = reinterpret_cast<uint2 *>(own->positions.d);
+      o.position_base = own->positions.claim(n_reads);
     }
   }
   uint32_t n_tasks = (uint32_t)n_reads * 2;
@@ -2230,42 +2221,58 @@ int gmx_engine_record_strands(gmx_engine *e, int on) try {
   return set_record_strands(e, on != 0);
 } GMX_GUARD_INT("gmx_engine_record_strands")
 
-int gmx_engine_record_outcomes(gmx_engine *e, int on) try {
+// The C ABI of a per-read log, shared by the outcome bytes and the position records.
+static int read_log_record(gmx_engine *e, GmxReadLog gmx_engine::*log, int on) {
   if (!e) {
     gmx_set_error("null engine");
     return GMX_EINVAL;
   }
-  e->record_outcomes = on != 0;
+  (e->*log).on = on != 0;
   return GMX_OK;
-} GMX_GUARD_INT("gmx_engine_record_outcomes")
+}
 
-int64_t gmx_engine_outcome_count(gmx_engine *e) try {
+static int64_t read_log_count(gmx_engine *e, GmxReadLog gmx_engine::*log) {
   if (!e) {
     gmx_set_error("null engine");
     return GMX_EINVAL;
   }
-  return (int64_t)e->outcome_count;
-} GMX_GUARD_INT("gmx_engine_outcome_count")
+  return (int64_t)(e->*log).count;
+}
 
-int gmx_engine_fetch_outcomes(gmx_engine *e, uint64_t first, uint64_t n, uint8_t *out) try {
+// reads first .. first + n of the log into `out`, once everything handed over has left its record (`name`: the caller's, for the
+// error texts)
+static int read_log_fetch(gmx_engine *e, GmxReadLog gmx_engine::*which, uint64_t first, uint64_t n, void *out, const char *name) {
   if (!e || (n && !out)) {
-    gmx_set_error("gmx_engine_fetch_outcomes: null argument");
+    gmx_set_error(std::string(name) + ": null argument");
     return GMX_EINVAL;
   }
-  if (first > e->outcome_count || n > e->outcome_count - first) {
-    gmx_set_error("gmx_engine_fetch_outcomes: reads " + std::to_string(first) + " .. " + std::to_string(first + n) + " of " +
-                  std::to_string(e->outcome_count) + " recorded");
+  const GmxReadLog &log = e->*which;
+  if (first > log.count || n > log.count - first) {
+    gmx_set_error(std::string(name) + ": reads " + std::to_string(first) + " .. " + std::to_string(first + n) + " of " +
+                  std::to_string(log.count) + " recorded");
     return GMX_EINVAL;
   }
   {
     int frc = flush_reset(e);
     if (frc) return frc;
-    if ((frc = log_settle(e))) return frc;  // (a task redone after a full log sets its bits then)
+    if ((frc = log_settle(e))) return frc;  // (a task redone after a full log leaves its bits and its record then)
   }
   HIP_TRY(hipSetDevice(e->opts.device));
   HIP_TRY(hipDeviceSynchronize());  // both workspaces' streams
-  if (n) HIP_TRY(hipMemcpy(out, reinterpret_cast<const uint8_t *>(e->d_outcomes) + first, n, hipMemcpyDeviceToHost));
+  if (n) HIP_TRY(hipMemcpy(out, reinterpret_cast<const uint8_t *>(log.d) + first * log.stride, n * log.stride, hipMemcpyDeviceToHost));
   return GMX_OK;
+}
+
+int gmx_engine_record_outcomes(gmx_engine *e, int on) try {
+  return read_log_record(e, &gmx_engine::outcomes, on);
+} GMX_GUARD_INT("gmx_engine_record_outcomes")
+
+int64_t gmx_engine_outcome_count(gmx_engine *e) try {
+  return read_log_count(e, &gmx_engine::outcomes);
+} GMX_GUARD_INT("gmx_engine_outcome_count")
+
+int gmx_engine_fetch_outcomes(gmx_engine *e, uint64_t first, uint64_t n, uint8_t *out) try {
+  return read_log_fetch(e, &gmx_engine::outcomes, first, n, out, "gmx_engine_fetch_outcomes");
 } GMX_GUARD_INT("gmx_engine_fetch_outcomes")
 
 // Counted records of e->log_counts into `out` (as far as they fit) and their length in words: one strand's counts, their sums,
@@ -2294,41 +2301,15 @@ static uint64_t emit_log_counts(const gmx_engine *e, LogForm which, uint32_t *ou
 }
 
 int gmx_engine_record_positions(gmx_engine *e, int on) try {
-  if (!e) {
-    gmx_set_error("null engine");
-    return GMX_EINVAL;
-  }
-  e->record_positions = on != 0;
-  return GMX_OK;
+  return read_log_record(e, &gmx_engine::positions, on);
 } GMX_GUARD_INT("gmx_engine_record_positions")
 
 int64_t gmx_engine_position_count(gmx_engine *e) try {
-  if (!e) {
-    gmx_set_error("null engine");
-    return GMX_EINVAL;
-  }
-  return (int64_t)e->position_count;
+  return read_log_count(e, &gmx_engine::positions);
 } GMX_GUARD_INT("gmx_engine_position_count")
 
 int gmx_engine_fetch_positions(gmx_engine *e, uint64_t first, uint64_t n, uint32_t *out) try {
-  if (!e || (n && !out)) {
-    gmx_set_error("gmx_engine_fetch_positions: null argument");
-    return GMX_EINVAL;
-  }
-  if (first > e->position_count || n > e->position_count - first) {
-    gmx_set_error("gmx_engine_fetch_positions: reads " + std::to_string(first) + " .. " + std::to_string(first + n) + " of " +
-                  std::to_string(e->position_count) + " recorded");
-    return GMX_EINVAL;
-  }
-  {
-    int frc = flush_reset(e);
-    if (frc) return frc;
-    if ((frc = log_settle(e))) return frc;  // (a task redone after a full log leaves its record then)
-  }
-  HIP_TRY(hipSetDevice(e->opts.device));
-  HIP_TRY(hipDeviceSynchronize());  // both workspaces' streams
-  if (n) HIP_TRY(hipMemcpy(out, e->d_positions + 4 * first, n * 16, hipMemcpyDeviceToHost));
-  return GMX_OK;
+  return read_log_fetch(e, &gmx_engine::positions, first, n, out, "gmx_engine_fetch_positions");
 } GMX_GUARD_INT("gmx_engine_fetch_positions")
 
 int64_t gmx_coverage_fetch_grouped_log(gmx_engine *e, uint32_t *out, uint64_t cap_words) try {
@@ -2384,7 +2365,7 @@ int gmx_coverage_import_grouped_log(gmx_engine *e, const uint32_t *records, uint
 
 }  // extern "C"
 
-uint64_t gmx_engine_outcome_epoch(const gmx_engine *e) { return e->outcome_epoch; }
+uint64_t gmx_engine_reset_epoch(const gmx_engine *e) { return e->reset_epoch; }
 
 void gmx_engine_raw(gmx_engine *e, GmxEngineRaw *out) {
   (void)flush_reset(e);

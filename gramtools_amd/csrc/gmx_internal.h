@@ -41,7 +41,7 @@ struct GmxEngineRaw {
   bool record_strands;  // two blocks (gmx_engine_record_strands): d_fused and n_fused change with it — take a fresh copy before an exchange
 };
 void gmx_engine_raw(gmx_engine *e, GmxEngineRaw *out);
-uint64_t gmx_engine_outcome_epoch(const gmx_engine *e);  // resets of the outcome buffer so far (gmx_group's ledger)
+uint64_t gmx_engine_reset_epoch(const gmx_engine *e);  // resets of the per-read logs so far (gmx_group's ledgers)
 // the engine's grouped log as counted records (gmx.h: gmx_coverage_fetch_grouped_log); import adds records to the
 // engine's host-side totals, after emptying them when `replace`
 int gmx_engine_log_export(gmx_engine *e, std::vector<uint32_t> &out);

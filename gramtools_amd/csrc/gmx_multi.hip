@@ -260,54 +260,92 @@ int gmx_exchange_peer(std::vector<Member> &ms) {
 struct gmx_group {
   std::vector<Member> ms;
   bool use_rccl = false;
-  // Per-read outcomes: which member recorded which range of the reads the group's feeds were handed, in hand-over order (the
-  // feeds deal contiguous ranges of the read index). Valid while no member's outcome buffer has been reset since (epochs).
-  struct OutcomeRange { uint64_t first, count; size_t member; uint64_t member_first; };
-  std::vector<OutcomeRange> ranges;
-  uint64_t n_outcomes = 0, epochs = 0;
-  // (the position records, gmx_engine_record_positions: the same ledger over the members' position counts — the two recordings
-  //  are switched independently, so a range of one need not be a range of the other)
-  std::vector<OutcomeRange> pos_ranges;
-  uint64_t n_positions = 0;
+  // A per-read log of the group (outcome bytes, position records): which member recorded which range of the reads the group's
+  // feeds were handed, in hand-over order (the feeds deal contiguous ranges of the read index). Valid while no member's logs have
+  // been reset since (epochs). One ledger per recording: the two are switched independently, so a range of one need not be a
+  // range of the other.
+  struct Ledger {
+    int64_t (*member_count)(gmx_engine *);  // the members' count this ledger follows
+    struct Range { uint64_t first, count; size_t member; uint64_t member_first; };
+    std::vector<Range> ranges;
+    uint64_t total = 0;
+    std::vector<uint64_t> before;  // around a feed: every member's count before it
+    uint64_t count_of(const Member &m) const { return (uint64_t)std::max<int64_t>(member_count(m.e), 0); }
+  };
+  enum { OUTCOMES = 0, POSITIONS = 1 };
+  Ledger ledgers[2] = {{gmx_engine_outcome_count}, {gmx_engine_position_count}};
+  uint64_t epochs = 0;
 };
 static uint64_t group_epochs(const gmx_group *g) {
   uint64_t s = 0;
-  for (auto const &m : g->ms) s += gmx_engine_outcome_epoch(m.e);
+  for (auto const &m : g->ms) s += gmx_engine_reset_epoch(m.e);
   return s;
 }
-static void group_ledger_sync(gmx_group *g) {  // a member was reset: the ranges before are gone with its bytes
+static void group_ledger_sync(gmx_group *g) {  // a member was reset: the ranges before are gone with its records
   const uint64_t now = group_epochs(g);
   if (now != g->epochs) {
-    g->ranges.clear();
-    g->n_outcomes = 0;
-    g->pos_ranges.clear();
-    g->n_positions = 0;
+    for (auto &l : g->ledgers) {
+      l.ranges.clear();
+      l.total = 0;
+    }
     g->epochs = now;
   }
 }
-// around a feed: what every member's count was before it, and the ranges the members recorded (member order = read order)
-// (entries [0, n): the outcome counts, [n, 2 n): the position counts)
-static std::vector<uint64_t> group_counts(gmx_group *g) {
+// Around a feed: notes every member's counts before it and, when it goes out of scope, the ranges the members recorded (member
+// order = read order).
+struct GroupNote {
+  gmx_group *g;
+  explicit GroupNote(gmx_group *g_) : g(g_) {
+    group_ledger_sync(g);
+    for (auto &l : g->ledgers) {
+      l.before.clear();
+      for (auto const &m : g->ms) l.before.push_back(l.count_of(m));
+    }
+  }
+  ~GroupNote() {
+    try {
+      for (auto &l : g->ledgers)
+        for (size_t i = 0; i < g->ms.size(); ++i) {
+          const uint64_t was = l.before[i], now = l.count_of(g->ms[i]);
+          if (now <= was) continue;
+          l.ranges.push_back({l.total, now - was, i, was});
+          l.total += now - was;
+        }
+    } catch (...) {
+    }
+  }
+};
+// reads first .. first + n of a ledger into `out`, `per_read` elements per read, range by range from the members that hold them (the
+// exchange is not involved: every member holds its own reads' records); `name`: the caller's, for the error texts
+template <class T>
+static int group_fetch(gmx_group *g, int which, uint64_t first, uint64_t n, T *out, uint64_t per_read,
+                       int (*member_fetch)(gmx_engine *, uint64_t, uint64_t, T *), const char *name) {
+  if (!g || (n && !out)) {
+    gmx_set_error(std::string(name) + ": null argument");
+    return GMX_EINVAL;
+  }
   group_ledger_sync(g);
-  std::vector<uint64_t> c;
-  for (auto const &m : g->ms) c.push_back((uint64_t)std::max<int64_t>(gmx_engine_outcome_count(m.e), 0));
-  for (auto const &m : g->ms) c.push_back((uint64_t)std::max<int64_t>(gmx_engine_position_count(m.e), 0));
-  return c;
+  const gmx_group::Ledger &l = g->ledgers[which];
+  if (first > l.total || n > l.total - first) {
+    gmx_set_error(std::string(name) + ": reads " + std::to_string(first) + " .. " + std::to_string(first + n) + " of " +
+                  std::to_string(l.total) + " recorded");
+    return GMX_EINVAL;
+  }
+  for (auto const &r : l.ranges) {
+    const uint64_t lo = std::max(first, r.first), hi = std::min(first + n, r.first + r.count);
+    if (lo >= hi) continue;
+    const int rc = member_fetch(g->ms[r.member].e, r.member_first + (lo - r.first), hi - lo, out + per_read * (lo - first));
+    if (rc) return rc;
+  }
+  return GMX_OK;
 }
-static void group_note(gmx_group *g, const std::vector<uint64_t> &before) {
-  for (size_t i = 0; i < g->ms.size(); ++i) {
-    const uint64_t now = (uint64_t)std::max<int64_t>(gmx_engine_outcome_count(g->ms[i].e), 0);
-    if (now <= before[i]) continue;
-    g->ranges.push_back({g->n_outcomes, now - before[i], i, before[i]});
-    g->n_outcomes += now - before[i];
+static int64_t group_count(gmx_group *g, int which) {
+  if (!g) {
+    gmx_set_error("null group");
+    return GMX_EINVAL;
   }
-  const size_t n = g->ms.size();
-  for (size_t i = 0; i < n; ++i) {
-    const uint64_t now = (uint64_t)std::max<int64_t>(gmx_engine_position_count(g->ms[i].e), 0);
-    if (now <= before[n + i]) continue;
-    g->pos_ranges.push_back({g->n_positions, now - before[n + i], i, before[n + i]});
-    g->n_positions += now - before[n + i];
-  }
+  group_ledger_sync(g);
+  return (int64_t)g->ledgers[which].total;
 }
 
 struct gmx_comm {
@@ -417,8 +455,7 @@ int gmx_group_map_reads_host(gmx_group *g, const uint8_t *reads, const uint64_t 
     return GMX_EINVAL;
   }
   const size_t n = g->ms.size();
-  const std::vector<uint64_t> recorded = group_counts(g);
-  struct Note { gmx_group *g; const std::vector<uint64_t> &b; ~Note() { try { group_note(g, b); } catch (...) {} } } note{g, recorded};
+  GroupNote note(g);
   if (n == 1) return gmx_map_reads_host(g->ms[0].e, reads, offsets, seeds, n_reads);
   std::vector<int> rcs(n, GMX_OK);
   std::vector<std::string> errs(n);
@@ -454,8 +491,7 @@ int gmx_group_map_reads_packed_host(gmx_group *g, const uint64_t *planes, const 
     return GMX_EINVAL;
   }
   const size_t n = g->ms.size();
-  const std::vector<uint64_t> recorded = group_counts(g);
-  struct Note { gmx_group *g; const std::vector<uint64_t> &b; ~Note() { try { group_note(g, b); } catch (...) {} } } note{g, recorded};
+  GroupNote note(g);
   if (n == 1) return gmx_map_reads_packed_host(g->ms[0].e, planes, offsets, uniform_len, seeds, skip, n_reads);
   if (!planes || !seeds || (!offsets && !uniform_len)) {
     gmx_set_error("gmx_group_map_reads_packed_host: null argument");
@@ -513,32 +549,11 @@ int gmx_group_map_reads_packed_host(gmx_group *g, const uint64_t *planes, const 
 } GMX_GUARD_INT("gmx_group_map_reads_packed_host")
 
 int64_t gmx_group_outcome_count(gmx_group *g) try {
-  if (!g) {
-    gmx_set_error("null group");
-    return GMX_EINVAL;
-  }
-  group_ledger_sync(g);
-  return (int64_t)g->n_outcomes;
+  return group_count(g, gmx_group::OUTCOMES);
 } GMX_GUARD_INT("gmx_group_outcome_count")
 
 int gmx_group_fetch_outcomes(gmx_group *g, uint64_t first, uint64_t n, uint8_t *out) try {
-  if (!g || (n && !out)) {
-    gmx_set_error("gmx_group_fetch_outcomes: null argument");
-    return GMX_EINVAL;
-  }
-  group_ledger_sync(g);
-  if (first > g->n_outcomes || n > g->n_outcomes - first) {
-    gmx_set_error("gmx_group_fetch_outcomes: reads " + std::to_string(first) + " .. " + std::to_string(first + n) + " of " +
-                  std::to_string(g->n_outcomes) + " recorded");
-    return GMX_EINVAL;
-  }
-  for (auto const &r : g->ranges) {  // (the exchange is not involved: every member holds its own reads' bytes)
-    const uint64_t lo = std::max(first, r.first), hi = std::min(first + n, r.first + r.count);
-    if (lo >= hi) continue;
-    const int rc = gmx_engine_fetch_outcomes(g->ms[r.member].e, r.member_first + (lo - r.first), hi - lo, out + (lo - first));
-    if (rc) return rc;
-  }
-  return GMX_OK;
+  return group_fetch(g, gmx_group::OUTCOMES, first, n, out, 1, gmx_engine_fetch_outcomes, "gmx_group_fetch_outcomes");
 } GMX_GUARD_INT("gmx_group_fetch_outcomes")
 
 int gmx_group_record_positions(gmx_group *g, int on) try {
@@ -554,32 +569,11 @@ int gmx_group_record_positions(gmx_group *g, int on) try {
 } GMX_GUARD_INT("gmx_group_record_positions")
 
 int64_t gmx_group_position_count(gmx_group *g) try {
-  if (!g) {
-    gmx_set_error("null group");
-    return GMX_EINVAL;
-  }
-  group_ledger_sync(g);
-  return (int64_t)g->n_positions;
+  return group_count(g, gmx_group::POSITIONS);
 } GMX_GUARD_INT("gmx_group_position_count")
 
 int gmx_group_fetch_positions(gmx_group *g, uint64_t first, uint64_t n, uint32_t *out) try {
-  if (!g || (n && !out)) {
-    gmx_set_error("gmx_group_fetch_positions: null argument");
-    return GMX_EINVAL;
-  }
-  group_ledger_sync(g);
-  if (first > g->n_positions || n > g->n_positions - first) {
-    gmx_set_error("gmx_group_fetch_positions: reads " + std::to_string(first) + " .. " + std::to_string(first + n) + " of " +
-                  std::to_string(g->n_positions) + " recorded");
-    return GMX_EINVAL;
-  }
-  for (auto const &r : g->pos_ranges) {  // (the exchange is not involved: every member holds its own reads' records)
-    const uint64_t lo = std::max(first, r.first), hi = std::min(first + n, r.first + r.count);
-    if (lo >= hi) continue;
-    const int rc = gmx_engine_fetch_positions(g->ms[r.member].e, r.member_first + (lo - r.first), hi - lo, out + 4 * (lo - first));
-    if (rc) return rc;
-  }
-  return GMX_OK;
+  return group_fetch(g, gmx_group::POSITIONS, first, n, out, 4, gmx_engine_fetch_positions, "gmx_group_fetch_positions");
 } GMX_GUARD_INT("gmx_group_fetch_positions")
 
 int gmx_group_sync_uploads(gmx_group *g) try {

@@ -2211,17 +2211,25 @@ int run_genotype(const Args &a) {
   }
   phase("engines created (HIP start-up, index upload)");
   gmx_engine *eng = gmx_group_engine(grp, 0);  // after the exchange every engine holds the totals: engine 0 is read back
-  // --read_outcomes: every engine keeps its reads' outcome bytes; which engine took which reads of the files, in file order,
-  // is noted here call by call (a chunk of a device route goes to one engine, a block of the host readers to the group)
-  const bool read_outcomes = a.has("read_outcomes");
-  struct OutcomeSeg { int engine; uint64_t first, n; };  // engine -1: reads first .. first + n of the group's feeds
-  std::vector<OutcomeSeg> outcome_segs;
-  if (read_outcomes)
+  // --read_outcomes, --read_positions: every engine keeps its reads' outcome bytes / position records; which engine took which
+  // reads of the files, in file order, is noted here call by call (a chunk of a device route goes to one engine, a block of the
+  // host readers to the group; the group's counts of the position records are the engines' own)
+  struct ReadLogSeg { int engine; uint64_t first, n; };  // engine -1: reads first .. first + n of the group's feeds
+  struct ReadLog {
+    bool on;
+    const char *name, *unit;  // in error messages: "read outcomes", "bytes"
+    uint64_t per_read;        // bytes
+    const unsigned char *header;
+    int64_t (*group_count)(gmx_group *);
+    int64_t (*engine_count)(gmx_engine *);
+    std::vector<ReadLogSeg> segs;
+  };
+  const unsigned char outcome_header[16] = {'G', 'M', 'X', 'O', 1, 0, 0, 0}, position_header[16] = {'G', 'M', 'X', 'P', 1, 0, 0, 0};
+  ReadLog outcome_log{a.has("read_outcomes"), "read outcomes", "bytes", 1, outcome_header, gmx_group_outcome_count, gmx_engine_outcome_count, {}};
+  ReadLog position_log{a.has("read_positions"), "read positions", "records", 16, position_header, gmx_group_position_count, gmx_engine_position_count, {}};
+  if (outcome_log.on)
     for (int d = 0; d < gmx_group_size(grp); ++d) GMX_CHECK(gmx_engine_record_outcomes(gmx_group_engine(grp, d), 1));
-  // --read_positions: the same bookkeeping for the engines' position records (their counts are the engines' own)
-  const bool read_positions = a.has("read_positions");
-  std::vector<OutcomeSeg> position_segs;
-  if (read_positions) GMX_CHECK(gmx_group_record_positions(grp, 1));
+  if (position_log.on) GMX_CHECK(gmx_group_record_positions(grp, 1));
   // --strand_coverage: every engine keeps the reads' and their reverse complements' coverage apart, across samples (a reset
   // zeroes both blocks); the exchange carries both
   const bool strand_coverage = a.has("strand_coverage");
@@ -2230,16 +2238,36 @@ int run_genotype(const Args &a) {
   if (strand_coverage || strand_bias) GMX_CHECK(gmx_group_record_strands(grp, 1));
   auto note_outcomes = [&](int engine, uint64_t n) {  // BEFORE the call that hands n reads to `engine` (or to the group)
     if (n == 0) return;
-    if (read_outcomes) {
-      const int64_t at = engine < 0 ? gmx_group_outcome_count(grp) : gmx_engine_outcome_count(gmx_group_engine(grp, engine));
-      if (at < 0) die(std::string("gram: read outcomes: ") + gmx_last_error());
-      outcome_segs.push_back(OutcomeSeg{engine, (uint64_t)at, n});
+    for (ReadLog *log : {&outcome_log, &position_log}) {
+      if (!log->on) continue;
+      const int64_t at = engine < 0 ? log->group_count(grp) : log->engine_count(gmx_group_engine(grp, engine));
+      if (at < 0) die(std::string("gram: ") + log->name + ": " + gmx_last_error());
+      log->segs.push_back(ReadLogSeg{engine, (uint64_t)at, n});
     }
-    if (read_positions) {
-      const int64_t at = engine < 0 ? gmx_group_position_count(grp) : gmx_engine_position_count(gmx_group_engine(grp, engine));
-      if (at < 0) die(std::string("gram: read positions: ") + gmx_last_error());
-      position_segs.push_back(OutcomeSeg{engine, (uint64_t)at, n});
+  };
+  // the engines' records of `log` put together in the order of the reads files: per_read_T elements of T per read
+  auto gather_read_log = [&](const ReadLog &log, uint64_t total_reads, auto group_fetch, auto engine_fetch, auto *out, uint64_t per_read_T) {
+    uint64_t at = 0;
+    for (auto const &sg : log.segs) {
+      if (at + sg.n > total_reads) die(std::string("gram: ") + log.name + ": more " + log.unit + " than reads");
+      if (sg.engine < 0)
+        GMX_CHECK(group_fetch(grp, sg.first, sg.n, out + per_read_T * at));
+      else
+        GMX_CHECK(engine_fetch(gmx_group_engine(grp, sg.engine), sg.first, sg.n, out + per_read_T * at));
+      at += sg.n;
     }
+    if (at != total_reads)
+      die(std::string("gram: ") + log.name + ": " + std::to_string(at) + " " + log.unit + " for " + std::to_string(total_reads) + " reads");
+  };
+  // G/read_*.bin: the log's 16-byte header with the read count, then per_read bytes per read
+  auto write_read_log = [&](const ReadLog &log, const std::string &bin_path, uint64_t total_reads, const unsigned char *payload) {
+    std::ofstream o(bin_path, std::ios::binary);
+    unsigned char header[16];
+    std::copy(log.header, log.header + 16, header);
+    for (int i = 0; i < 8; ++i) header[8 + i] = (unsigned char)((total_reads >> (8 * i)) & 0xFF);
+    o.write(reinterpret_cast<const char *>(header), 16);
+    o.write(reinterpret_cast<const char *>(payload), (std::streamsize)(log.per_read * total_reads));
+    close_checked(o, bin_path);
   };
   // workspace for the calls the feed will make (a block of a reads file per call, at most 1 M reads per engine)
   for (int d = 0; d < gmx_group_size(grp); ++d) GMX_CHECK(gmx_engine_reserve_packed(gmx_group_engine(grp, d), info.is_nested ? 4u << 20 : 3u << 19 /* (a decoded BGZF chunk of 150 bp reads: 1.46 M) */, ((info.is_nested ? 24ull : 6ull) << 20) + 64));
@@ -2264,8 +2292,8 @@ int run_genotype(const Args &a) {
   phase("base error rate of the first 10 000 reads");
   if (sample_i > 0) {  // the accumulators and read counters of the sample before
     for (int d = 0; d < gmx_group_size(grp); ++d) GMX_CHECK(gmx_engine_reset(gmx_group_engine(grp, d)));
-    outcome_segs.clear();
-    position_segs.clear();
+    outcome_log.segs.clear();
+    position_log.segs.clear();
     g_feed = FeedTimes{};
   }
   std::cout << "Running quasimap" << std::endl;
@@ -2484,27 +2512,11 @@ int run_genotype(const Args &a) {
 
   // The three coverage files and read_stats.json are written on a thread of their own, beside the genotyping model below
   // (round 5: at configs[1] they were 42 ms of a call whose mapping takes 24; nothing below reads what they write).
-  if (read_outcomes) {  // G/read_outcomes.bin + .json: the engines' bytes put together in the order of the reads files
+  if (outcome_log.on) {  // G/read_outcomes.bin + .json
     std::vector<uint8_t> bytes(std::max<uint64_t>(total_reads, 1));
-    uint64_t at = 0;
-    for (auto const &sg : outcome_segs) {
-      if (at + sg.n > total_reads) die("gram: read outcomes: more bytes than reads");
-      if (sg.engine < 0)
-        GMX_CHECK(gmx_group_fetch_outcomes(grp, sg.first, sg.n, bytes.data() + at));
-      else
-        GMX_CHECK(gmx_engine_fetch_outcomes(gmx_group_engine(grp, sg.engine), sg.first, sg.n, bytes.data() + at));
-      at += sg.n;
-    }
-    if (at != total_reads) die("gram: read outcomes: " + std::to_string(at) + " bytes for " + std::to_string(total_reads) + " reads");
-    const std::string bin_path = join(run_dir, "read_outcomes.bin"), json_path = join(run_dir, "read_outcomes.json");
-    {
-      std::ofstream o(bin_path, std::ios::binary);
-      unsigned char header[16] = {'G', 'M', 'X', 'O', 1, 0, 0, 0};
-      for (int i = 0; i < 8; ++i) header[8 + i] = (unsigned char)((total_reads >> (8 * i)) & 0xFF);
-      o.write(reinterpret_cast<const char *>(header), 16);
-      o.write(reinterpret_cast<const char *>(bytes.data()), (std::streamsize)total_reads);
-      close_checked(o, bin_path);
-    }
+    gather_read_log(outcome_log, total_reads, gmx_group_fetch_outcomes, gmx_engine_fetch_outcomes, bytes.data(), 1);
+    const std::string json_path = join(run_dir, "read_outcomes.json");
+    write_read_log(outcome_log, join(run_dir, "read_outcomes.bin"), total_reads, bytes.data());
     uint64_t by_value[256] = {0}, by_code[4] = {0};
     for (uint64_t i = 0; i < total_reads; ++i) {
       ++by_value[bytes[i]];
@@ -2523,29 +2535,15 @@ int run_genotype(const Args &a) {
     o << "}}\n";
     close_checked(o, json_path);
   }
-  if (read_positions) {  // G/read_positions.bin + .json: the engines' records put together in the order of the reads files
+  if (position_log.on) {  // G/read_positions.bin + .json
     std::vector<uint32_t> words(4 * std::max<uint64_t>(total_reads, 1));
-    uint64_t at = 0;
-    for (auto const &sg : position_segs) {
-      if (at + sg.n > total_reads) die("gram: read positions: more records than reads");
-      if (sg.engine < 0)
-        GMX_CHECK(gmx_group_fetch_positions(grp, sg.first, sg.n, words.data() + 4 * at));
-      else
-        GMX_CHECK(gmx_engine_fetch_positions(gmx_group_engine(grp, sg.engine), sg.first, sg.n, words.data() + 4 * at));
-      at += sg.n;
-    }
-    if (at != total_reads) die("gram: read positions: " + std::to_string(at) + " records for " + std::to_string(total_reads) + " reads");
-    const std::string bin_path = join(run_dir, "read_positions.bin"), json_path = join(run_dir, "read_positions.json");
+    gather_read_log(position_log, total_reads, gmx_group_fetch_positions, gmx_engine_fetch_positions, words.data(), 4);
+    const std::string json_path = join(run_dir, "read_positions.json");
     {
-      std::ofstream o(bin_path, std::ios::binary);
-      unsigned char header[16] = {'G', 'M', 'X', 'P', 1, 0, 0, 0};
-      for (int i = 0; i < 8; ++i) header[8 + i] = (unsigned char)((total_reads >> (8 * i)) & 0xFF);
-      o.write(reinterpret_cast<const char *>(header), 16);
       std::vector<unsigned char> le(16 * std::max<uint64_t>(total_reads, 1));  // (little-endian whatever the host)
       for (uint64_t i = 0; i < 4 * total_reads; ++i)
         for (int k = 0; k < 4; ++k) le[4 * i + k] = (unsigned char)((words[i] >> (8 * k)) & 0xFF);
-      o.write(reinterpret_cast<const char *>(le.data()), (std::streamsize)(16 * total_reads));
-      close_checked(o, bin_path);
+      write_read_log(position_log, join(run_dir, "read_positions.bin"), total_reads, le.data());
     }
     uint64_t mapped = 0, unique = 0, multi = 0, hist[5] = {0};  // n: 1 | 2 | 3-10 | 11-100 | above 100
     for (uint64_t t = 0; t < 2 * total_reads; ++t) {

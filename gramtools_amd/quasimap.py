@@ -29,6 +29,18 @@ def _p(arr, ctype):
     return arr.ctypes.data_as(C.POINTER(ctype))
 
 
+def _fetch_read_log(fetch, handle, what, count, first, n, per_read, dtype):
+    """Records first .. first + n (default: all `count`) of the per-read log `what` of an engine or a group, copied by the
+    library's `fetch`: an array of `dtype` with the dimensions `per_read` behind the reads'."""
+    if n is None:
+        n = count - first
+    if first < 0 or n < 0 or first + n > count:
+        raise ValueError(f"{what}: reads {first} .. {first + n} of {count} recorded")
+    out = np.zeros((max(n, 1),) + per_read, dtype=dtype)
+    check(fetch(handle, first, n, _p(out, np.ctypeslib.as_ctypes_type(dtype))))
+    return out[:n]
+
+
 def encode_dna_bases(seq: str) -> np.ndarray:
     """A,C,G,T (any case) -> 1,2,3,4; any other character gives an empty read (common/utils.cpp:73-92)."""
     b = np.frombuffer(seq.encode("ascii", "replace"), dtype=np.uint8)
@@ -562,14 +574,7 @@ class Quasimapper:
         """The outcome bytes of reads first .. first + n (default: all recorded), in the order the reads were handed over:
         bits 0-1 the forward task's code, 2-3 the reverse-complement task's (0 skipped, 1 missing k-mer, 2 no exact mapping,
         3 exactly mapped), bit 4 / 5 that task's selection drew among several mapping instances (gmx_engine_fetch_outcomes)."""
-        count = self.outcome_count()
-        if n is None:
-            n = count - first
-        if first < 0 or n < 0 or first + n > count:
-            raise ValueError(f"outcomes: reads {first} .. {first + n} of {count} recorded")
-        out = np.zeros(max(n, 1), dtype=np.uint8)
-        check(self.lib.gmx_engine_fetch_outcomes(self.h, first, n, _p(out, C.c_uint8)))
-        return out[:n]
+        return _fetch_read_log(self.lib.gmx_engine_fetch_outcomes, self.h, "outcomes", self.outcome_count(), first, n, (), np.uint8)
 
     def record_strands(self, on: bool = True):
         """Coverage per strand (gmx_engine_record_strands): what the reads as given recorded and what their reverse complements
@@ -589,14 +594,7 @@ class Quasimapper:
         an (n, 4) uint32 array [pos_fwd, n_fwd, pos_rc, n_rc] — n the number of mapping instances of the orientation (0: not
         exactly mapped), pos the 0-based index into the linearised PRG of the read's first base, the smallest among the
         instances the selection chose from (gmx_engine_fetch_positions)."""
-        count = self.position_count()
-        if n is None:
-            n = count - first
-        if first < 0 or n < 0 or first + n > count:
-            raise ValueError(f"positions: reads {first} .. {first + n} of {count} recorded")
-        out = np.zeros((max(n, 1), 4), dtype=np.uint32)
-        check(self.lib.gmx_engine_fetch_positions(self.h, first, n, _p(out, C.c_uint32)))
-        return out[:n]
+        return _fetch_read_log(self.lib.gmx_engine_fetch_positions, self.h, "positions", self.position_count(), first, n, (4,), np.uint32)
 
     def enable_timing(self, on=True):
         check(self.lib.gmx_engine_enable_timing(self.h, 1 if on else 0))
@@ -975,14 +973,7 @@ class QuasimapperGroup:
 
     def outcomes(self, first: int = 0, n: int = None) -> np.ndarray:
         """Outcome bytes of the reads handed to the group's feeds, in that order (gmx_group_fetch_outcomes)."""
-        count = self.outcome_count()
-        if n is None:
-            n = count - first
-        if first < 0 or n < 0 or first + n > count:
-            raise ValueError(f"outcomes: reads {first} .. {first + n} of {count} recorded")
-        out = np.zeros(max(n, 1), dtype=np.uint8)
-        check(self.lib.gmx_group_fetch_outcomes(self.h, first, n, _p(out, C.c_uint8)))
-        return out[:n]
+        return _fetch_read_log(self.lib.gmx_group_fetch_outcomes, self.h, "outcomes", self.outcome_count(), first, n, (), np.uint8)
 
     def _member(self, member: int) -> Quasimapper:
         view = Quasimapper.__new__(Quasimapper)
@@ -998,14 +989,7 @@ class QuasimapperGroup:
 
     def positions(self, first: int = 0, n: int = None) -> np.ndarray:
         """Position records of the reads handed to the group's feeds, in that order (gmx_group_fetch_positions)."""
-        count = self.position_count()
-        if n is None:
-            n = count - first
-        if first < 0 or n < 0 or first + n > count:
-            raise ValueError(f"positions: reads {first} .. {first + n} of {count} recorded")
-        out = np.zeros((max(n, 1), 4), dtype=np.uint32)
-        check(self.lib.gmx_group_fetch_positions(self.h, first, n, _p(out, C.c_uint32)))
-        return out[:n]
+        return _fetch_read_log(self.lib.gmx_group_fetch_positions, self.h, "positions", self.position_count(), first, n, (4,), np.uint32)
 
     def coverage(self, member: int = 0, strand=None) -> Coverage:
         """Coverage held by engine `member` (after :meth:`allreduce`: the totals of the whole job, on every member); with

@@ -284,6 +284,44 @@ def test_every_feed_gives_the_same_bytes(monkeypatch, twin):
                 assert qm.outcomes().tolist() == want[:50].tolist()
 
 
+def tiled(reads, seeds, copies):
+    """(flat, offsets, seeds) of one launch: `copies` copies of the reads back to back, put together with numpy."""
+    flat, offs = flatten_reads(reads)
+    ends = np.cumsum(np.tile(np.diff(offs.astype(np.int64)), copies))
+    return np.tile(flat, copies), np.concatenate([[0], ends]).astype(np.uint64), np.tile(np.asarray(seeds, dtype=np.uint32), copies)
+
+
+def test_a_full_buffer_grows_and_carries_the_recorded_bytes_over(monkeypatch):
+    """The buffer starts at 1 MiB. Four launches of 430 copies of the first 611 reads of the flat case, 262 730 reads each: the fourth
+    needs 1 050 920 bytes and makes the buffer grow with 788 190 bytes recorded — no multiple of 4, and 611 is odd: the launches
+    share words, the carry-over is rounded to whole words. With GMX_TWIN=1 the launch before may still be in flight on the other
+    workspace. Every byte is the oracle's for its read (which depends on the read alone); a reset clears the grown buffer."""
+    monkeypatch.setenv("GMX_TWIN", "1")
+    prg, k, reads = flat_case()
+    reads = reads[:611]
+    seeds = master_seeds(7, [len(reads)])
+    want, _ = oracle_bytes(prg, k, reads)
+    copies, launches = 430, 4
+    per_launch = copies * len(reads)
+    assert (launches - 1) * per_launch < (1 << 20) < launches * per_launch and ((launches - 1) * per_launch) % 4
+    flat, offs, s = tiled(reads, seeds, copies)
+    qm = Quasimapper(Index(prg, k))
+    qm.record_outcomes(True)
+    assert qm.lib.gmx_engine_second_stream(qm.h)
+    for _ in range(launches):
+        qm.map_reads(flat, offs, s)
+    qm.sync()
+    assert qm.outcome_count() == launches * per_launch
+    got = qm.outcomes()
+    bad = np.flatnonzero(got != np.tile(want, launches * copies))
+    assert got.shape == (launches * per_launch,) and bad.size == 0, [(int(i), fields(got[i]), fields(want[i % len(reads)])) for i in bad[:10]]
+    qm.reset()  # the grown buffer is cleared over its used prefix
+    one_flat, one_offs = flatten_reads(reads)
+    qm.map_reads(one_flat, one_offs, seeds)
+    assert qm.outcome_count() == len(reads)
+    assert qm.outcomes().tolist() == want.tolist()
+
+
 def test_recording_off_leaves_nothing_and_changes_nothing():
     prg, k, reads = flat_case()
     ix = Index(prg, k)

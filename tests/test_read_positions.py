@@ -17,7 +17,7 @@ from oracle.oracle import RNG_LEMIRE
 from gramtools_amd import Index, Quasimapper, master_seeds, pack_reads
 from gramtools_amd.synth import random_ref, simulate_snp_reads, snp_prg
 from test_many_instances import tandem_prg, tandem_reads
-from test_read_outcomes import FEEDS, flat_case, nested_case, repeat_case, revcomp, run_feed
+from test_read_outcomes import FEEDS, flat_case, nested_case, repeat_case, revcomp, run_feed, tiled
 
 pytestmark = pytest.mark.gpu
 
@@ -210,6 +210,35 @@ def test_every_route_gives_the_same_records(monkeypatch, twin):
                 assert qm.position_count() == 0
                 run_feed(qm, reads[:50], seeds[:50], feed, chunk)
                 assert_same(qm.positions(), want[:50], (feed, "after the second reset"))
+
+
+def test_a_full_buffer_grows_and_carries_the_records_over(monkeypatch):
+    """The buffer starts at 1 MiB, 65 536 records. Four launches of 27 copies of the first 611 reads of the flat case, 16 497 reads
+    each: the fourth needs 65 988 records and makes the buffer grow with 49 491 recorded. With GMX_TWIN=1 the launch before may
+    still be in flight on the other workspace. Every record is the oracle's for its read and seed (it depends on nothing else), a
+    slice across the carried / new boundary too; a reset clears the grown buffer."""
+    monkeypatch.setenv("GMX_TWIN", "1")
+    prg, k, reads, seeds, want, _ = case("flat")
+    reads, seeds, want = reads[:611], seeds[:611], want[:611]
+    copies, launches = 27, 4
+    per_launch = copies * len(reads)
+    assert (launches - 1) * per_launch < (1 << 16) < launches * per_launch
+    flat, offs, s = tiled(reads, seeds, copies)
+    qm = Quasimapper(Index(prg, k))
+    qm.record_positions(True)
+    assert qm.lib.gmx_engine_second_stream(qm.h)
+    for _ in range(launches):
+        qm.map_reads(flat, offs, s)
+    qm.sync()
+    assert qm.position_count() == launches * per_launch
+    all_want = np.tile(want, (launches * copies, 1))
+    assert_same(qm.positions(), all_want, "after the growth")
+    assert_same(qm.positions(49_000, 1_000), all_want[49_000:50_000], "across the carried / new boundary")
+    qm.reset()  # the grown buffer is cleared over its used prefix
+    one_flat, one_offs = flatten_reads(reads)
+    qm.map_reads(one_flat, one_offs, seeds)
+    assert qm.position_count() == len(reads)
+    assert_same(qm.positions(), want, "after the reset")
 
 
 @pytest.mark.parametrize("name", ["nested", "repeat", "half_sited"])
