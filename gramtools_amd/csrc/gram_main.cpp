@@ -1019,46 +1019,6 @@ bool parse_fastq_file(const std::string &path, int threads, Sink sink) {
     if (_rc < 0) die(std::string("gram: ") + #expr + " failed: " + gmx_last_error()); \
   } while (0)
 
-// ---- BGZF files decoded on the GPU (include/gmx.h gmx_ingest_*, gmx_ingest.hip) ------------------------------------------
-// A file that is BGZF members from its first byte to its last (bgzip, htslib, BCL Convert) is handed to the device as it
-// lies in the page cache: the member table is walked here (18 bytes per member), the deflate data of a few thousand members
-// at a time is copied into page-locked memory by all threads and uploaded, and HIP kernels inflate it, check every member's
-// CRC-32, find the records and pack the bases — the host inflates nothing (sixteen cores manage 32-48 M reads/s of BGZF; the
-// mapping kernels take 2 400 M). `on_chunk(result, slot)` is called for every chunk in file order, with the chunk's reads in
-// HBM; it must enqueue what reads them and call gmx_ingest_release_after.
-// Returns  0  the whole file was delivered
-//          1  declined before anything was delivered (not pure BGZF, or not four-line FASTQ: the caller's other readers decide)
-//          2  a chunk could not be decoded after `delivered` reads had been: the caller re-reads the file on the host, which
-//             either reports the damage or — a defect of the device decoder — delivers the rest
-static bool bgzf_member_at(const unsigned char *in, size_t size, size_t at, gmx_bgzf_member *m, size_t *next) {
-  auto le16 = [](const unsigned char *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; };
-  auto le32 = [](const unsigned char *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; };
-  if (at + 18 > size) return false;
-  const unsigned char *p = in + at;
-  if (p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || p[3] != 4) return false;
-  const uint32_t xlen = le16(p + 10);
-  if (at + 12 + xlen > size) return false;
-  uint32_t bsize = 0;
-  bool found = false;
-  for (uint32_t x = 0; x + 4 <= xlen;) {
-    const unsigned char *f = p + 12 + x;
-    const uint32_t slen = le16(f + 2);
-    if (f[0] == 'B' && f[1] == 'C' && slen == 2 && x + 6 <= xlen) {
-      bsize = le16(f + 4) + 1;
-      found = true;
-    }
-    x += 4 + slen;
-  }
-  if (!found || bsize < 12 + xlen + 8 || at + bsize > size) return false;
-  m->offset = at + 12 + xlen;
-  m->size = bsize - 12 - xlen - 8;
-  m->crc32 = le32(p + bsize - 8);
-  m->isize = le32(p + bsize - 4);
-  m->reserved = 0;
-  *next = at + bsize;
-  return m->isize <= 65536u;
-}
-
 // What a reads file holds, as the general reader (SeqReader::next) decides it: by the first byte of the first line that is not
 // blank ('@' FASTQ, '>' FASTA, anything else one read per line); BAM by its magic. Only the head of the file is looked at; zlib inflates it where
 // the file is compressed (BGZF and plain gzip alike). The device chain scans all three (gmx_ingest_set_format); every ingest_*
@@ -1081,655 +1041,7 @@ static const char *reads_format_scanner() {
   return g_reads_format == GMX_INGEST_FORMAT_BAM ? "BAM record chain" : g_reads_format == GMX_INGEST_FORMAT_FASTA ? "FASTA scanner" : g_reads_format == GMX_INGEST_FORMAT_LINES ? "one-read-per-line scanner" : "FASTQ scanner";
 }
 
-struct DeviceFeed {  // one per process: the ingest object and its page-locked staging, sized by the largest file seen
-  gmx_ingest *ing = nullptr;
-  uint64_t max_text = 0;
-  int device = 0;
-  HostBuf<uint8_t> stage[4];  // (BGZF uses three: chunk i + 2's bytes are staged while chunks i and i + 1 are on the device; plain text four: ingest_text_file)
-  ~DeviceFeed() {
-    if (ing) gmx_ingest_destroy(ing);
-  }
-};
-static DeviceFeed g_device_feed;                             // the first (or only) engine's
-static std::vector<std::unique_ptr<DeviceFeed>> g_more_feeds;  // the other engines' (several GPUs: chunks dealt round)
-
-// the ingest object and its staging buffers ahead of the first BGZF file (called beside the index load: device memory for a
-// chunk and two page-locked buffers take 30 ms to come by)
-static bool hipSetDeviceForPrewarm(int) { return true; }  // (gmx_ingest_create selects the device itself)
-static void device_feed_prepare(int device, uint64_t want_text, uint64_t stage_bytes, DeviceFeed *which = nullptr) {
-  DeviceFeed &df = which ? *which : g_device_feed;
-  if (!df.ing || df.max_text < want_text || df.device != device) {
-    if (df.ing) gmx_ingest_destroy(df.ing);
-    df.ing = nullptr;
-    df.max_text = 0;
-    if (gmx_ingest_create(device, want_text, &df.ing) != GMX_OK) return;
-    df.max_text = want_text;
-    df.device = device;
-  }
-  for (auto &st : df.stage)
-    if (st.size() < stage_bytes) st.resize(stage_bytes);
-}
-static uint64_t device_feed_members() {
-  uint64_t k = 7168 * g_ingest_member_scale;  // one round of the wavefronts an MI355X holds of gmx_inflate_kernel (28 per CU)
-  if (const char *e = getenv("GMX_INGEST_MEMBERS")) k = std::max<uint64_t>(1, (uint64_t)atoll(e));
-  return k;
-}
-static uint64_t device_feed_text_for(uint64_t file_text) {
-  return std::min<uint64_t>(std::max<uint64_t>(std::min<uint64_t>(file_text, device_feed_members() * 65536ull), 1u << 16) + (1u << 16), 3ull << 30);
-}
-
-template <class OnChunk>
-int ingest_bgzf_file(const std::string &path, int threads, int device, OnChunk on_chunk, uint64_t *delivered) {
-  *delivered = 0;
-  int fd = open(path.c_str(), O_RDONLY);
-  if (fd < 0) return 1;
-  struct stat sb;
-  if (fstat(fd, &sb) != 0 || sb.st_size < 28) {
-    close(fd);
-    return 1;
-  }
-  const size_t size = (size_t)sb.st_size;
-  void *mp = mmap(nullptr, size, PROT_READ, MAP_PRIVATE | MAP_NORESERVE, fd, 0);
-  close(fd);
-  if (mp == MAP_FAILED) return 1;
-  const unsigned char *in = static_cast<const unsigned char *>(mp);
-  struct Unmap {
-    void *p;
-    size_t n;
-    ~Unmap() { munmap(p, n); }
-  } unmap{mp, size};
-  // The member table is walked a chunk at a time, beside the device (round 5: the whole table first cost 7 ms of a 22 000-member file
-  // before the first byte went up). Every byte of the file must belong to a BGZF member: a file that stops being BGZF behind chunks
-  // already delivered is handed to the host reader, which drops what was mapped (return value 2).
-  {  // not BGZF at its first byte: declined BEFORE the ingest is sized for it (round 6: a plain FASTQ of 1.26 GB had the ingest the
-     // prewarm thread made for its text chunks thrown away and one for 470 MB chunks made here — 40 ms — just to be declined)
-    gmx_bgzf_member m0;
-    size_t next0;
-    if (!bgzf_member_at(in, size, 0, &m0, &next0)) return 1;
-  }
-  DeviceFeed &df = g_device_feed;
-  device_feed_prepare(device, device_feed_text_for((uint64_t)size * 6), 0);  // (as the call beside the index load sized it)
-  if (!df.ing) return 1;
-  gmx_ingest *ing = df.ing;
-  GMX_CHECK(gmx_ingest_reset(ing));
-  GMX_CHECK(gmx_ingest_set_format(ing, g_reads_format));
-  const bool bam = g_reads_format == GMX_INGEST_FORMAT_BAM;
-  if (bam) {  // the header's length in the file's text: zlib inflates the file's head (a header that cannot be read: the host reader says why)
-    SeqReader head(path);
-    if (!head.is_bam()) return 1;
-    GMX_CHECK(gmx_ingest_set_bam_header(ing, head.bam_header_bytes()));
-  }
-  // (a chunk holds at most what the ingest's member table holds: a file of many tiny members must not be refused by the submit)
-  const uint64_t kMembers = std::min<uint64_t>(device_feed_members(), gmx_ingest_max_members(ing));
-  const uint64_t max_text = gmx_ingest_max_text(ing), max_comp = gmx_ingest_max_compressed(ing);
-  struct Chunk {
-    std::vector<gmx_bgzf_member> rel;  // its members, offsets from lo
-    size_t lo = 0, hi = 0;             // file bytes their deflate data spans
-  };
-  size_t walk_at = 0;
-  auto skip_empty = [&]() -> bool {  // to the next member that holds text; false: the bytes there are no BGZF member
-    while (walk_at < size) {
-      gmx_bgzf_member m;
-      size_t next;
-      if (!bgzf_member_at(in, size, walk_at, &m, &next)) return false;
-      if (m.isize) break;
-      walk_at = next;  // (empty members — the EOF marker — hold nothing)
-    }
-    return true;
-  };
-  // the next chunk of members: at most kMembers, and what the ingest has room for. 1: a chunk, 0: the file's end, -1: not BGZF
-  auto next_chunk = [&](Chunk &c) -> int {
-    c.rel.clear();
-    c.lo = c.hi = 0;
-    uint64_t text = 0;
-    while (walk_at < size) {
-      gmx_bgzf_member m;
-      size_t next;
-      if (!bgzf_member_at(in, size, walk_at, &m, &next)) return -1;
-      if (m.isize) {
-        if (c.rel.empty()) c.lo = (size_t)m.offset;
-        if (c.rel.size() >= kMembers || text + m.isize > max_text || m.offset + m.size - c.lo > max_comp) break;
-        text += m.isize;
-        c.hi = (size_t)(m.offset + m.size);
-        m.offset -= c.lo;
-        c.rel.push_back(m);
-      }
-      walk_at = next;
-    }
-    if (c.rel.empty()) return walk_at < size ? -1 : 0;  // (a member the ingest has no room for: cannot happen with <= 64 KB members)
-    return skip_empty() ? 1 : -1;                        // (so that walk_at == size tells a chunk it is the file's last)
-  };
-  const unsigned T = (unsigned)std::max(1, std::min(threads, 64));
-  // Chunk i + 2's bytes are staged (page cache -> page-locked memory, 5 ms a chunk) and submitted while chunks i and i + 1 are on the
-  // device (the ingest's three slots): the device never waits for the host's memcpy
-  // (round 5: staged inside the submit, the copy sat between a chunk's result and the next chunk's upload — a GPU idle for 6 ms of
-  // every 13). Three staging buffers: the one chunk i + 2 takes was chunk i - 1's, whose upload is long done (it has been waited for).
-  Chunk ring[3];
-  bool last_of_file[3] = {false, false, false};
-  size_t n_staged = 0;  // chunks walked and staged so far
-  bool at_end = false, bad_walk = false;
-  auto stage = [&]() -> bool {  // the next chunk, into slot n_staged % 3; false: there is none
-    if (at_end || bad_walk) return false;
-    Chunk &c = ring[n_staged % 3];
-    const int rc = next_chunk(c);
-    if (rc <= 0) {
-      at_end = rc == 0;
-      bad_walk = rc < 0;
-      return false;
-    }
-    last_of_file[n_staged % 3] = walk_at >= size;
-    HostBuf<uint8_t> &st = df.stage[n_staged % 3];
-    const size_t n = c.hi - c.lo;
-    st.resize(n + 64);
-    parallel_for(T, [&](unsigned t) {  // the compressed bytes, from the page cache into page-locked memory
-      const size_t a = n * t / T, b = n * (t + 1) / T;
-      if (b > a) memcpy(st.data() + a, in + c.lo + a, b - a);
-    });
-    ++n_staged;
-    return true;
-  };
-  size_t n_submitted = 0;
-  auto submit = [&]() {  // chunk n_submitted (staged)
-    const size_t ci = n_submitted;
-    const Chunk &c = ring[ci % 3];
-    GMX_CHECK(gmx_ingest_submit_bgzf(ing, (int)(ci % 3), df.stage[ci % 3].data(), c.hi - c.lo, c.rel.data(), c.rel.size(), last_of_file[ci % 3] ? 1 : 0));
-    ++n_submitted;
-    feed_trace("chunk submitted to the device");
-  };
-  if (!skip_empty()) return 1;
-  if (!stage()) return bad_walk ? 1 : 0;  // (0: no reads at all)
-  submit();
-  feed_trace("first chunk on its way; the member table is walked beside the device");
-  if (stage()) submit();
-  for (size_t ci = 0; ci < n_submitted; ++ci) {
-    // chunk ci + 2 goes to the device BEFORE chunk ci is waited for (three slots: its slot is chunk ci - 1's, waited for and handed to
-    // the engine): two inflate kernels are queued behind the one in flight, and a kernel's last wavefronts never have the GPU alone
-    if (n_staged == n_submitted) stage();
-    if (n_staged > n_submitted) submit();
-    gmx_ingest_result res;
-    GMX_CHECK(gmx_ingest_wait(ing, (int)(ci % 3), &res));
-    feed_trace(bam ? "BAM chunk chained and packed" : "chunk decoded");
-    if (const char *tf = getenv("GMX_INGEST_TEST_FAIL_CHUNK"))  // test hook: the device decoder "gives up" on this chunk (tests/test_ingest.py)
-      if ((size_t)atoll(tf) == ci) res.status |= GMX_INGEST_BAD_MEMBER;
-    if (res.status) {
-      for (size_t cj = ci + 1; cj < n_submitted; ++cj) {  // (the chunks behind are in flight: let them finish before the slots are reused)
-        gmx_ingest_result drop;
-        GMX_CHECK(gmx_ingest_wait(ing, (int)(cj % 3), &drop));
-      }
-      if (bam) return 2;  // whatever the status: the host reader takes the file over, and names a malformed record
-      const bool decoder = (res.status & (GMX_INGEST_BAD_MEMBER | GMX_INGEST_BAD_CRC | GMX_INGEST_TOO_MANY_LINES)) != 0;
-      if (!decoder) {  // the text itself is not four-line FASTQ: the host's fast path would say the same
-        if (*delivered == 0) return 1;
-        if (g_reads_format != GMX_INGEST_FORMAT_FASTQ) return 2;  // (FASTA / one read per line: the general reader takes over)
-        die("gram: " + path + ": irregular FASTQ record after the first " + std::to_string(*delivered) +
-            " reads (multi-line or blank lines); decompress and reformat, or use a four-line FASTQ");
-      }
-      // a member the kernels would not decode, or lines of a few bytes (more records than the ingest has room for): the host reader's
-      return *delivered == 0 && !(res.status & (GMX_INGEST_BAD_MEMBER | GMX_INGEST_BAD_CRC)) ? 1 : 2;
-    }
-    on_chunk(res, (int)(ci % 3));
-    *delivered += res.n_reads;
-  }
-  if (bad_walk) return *delivered == 0 && !bam ? 1 : 2;  // bytes that are no BGZF member behind the chunks delivered: the host reader's
-  return 0;
-}
-
-// The same over SEVERAL engines (`--devices`): one ingest per engine, the file's chunks dealt round. Every chunk
-// is uploaded and inflated ahead (two per device in flight); the chunks are scanned in file order, each with the cut record of
-// the chunk before — which lies on another device — handed over through the host (a few hundred bytes). on_chunk(result, k, slot):
-// engine k's ingest holds the chunk's reads. Return values as ingest_bgzf_file.
-template <class OnChunk>
-int ingest_bgzf_file_dealt(const std::string &path, int threads, const std::vector<int> &devs, OnChunk on_chunk, uint64_t *delivered) {
-  *delivered = 0;
-  const size_t N = devs.size();
-  int fd = open(path.c_str(), O_RDONLY);
-  if (fd < 0) return 1;
-  struct stat sb;
-  if (fstat(fd, &sb) != 0 || sb.st_size < 28) {
-    close(fd);
-    return 1;
-  }
-  const size_t size = (size_t)sb.st_size;
-  void *mp = mmap(nullptr, size, PROT_READ, MAP_PRIVATE | MAP_NORESERVE, fd, 0);
-  close(fd);
-  if (mp == MAP_FAILED) return 1;
-  const unsigned char *in = static_cast<const unsigned char *>(mp);
-  struct Unmap {
-    void *p;
-    size_t n;
-    ~Unmap() { munmap(p, n); }
-  } unmap{mp, size};
-  std::vector<gmx_bgzf_member> members;
-  members.reserve(size / 16000 + 16);
-  for (size_t at = 0; at < size;) {
-    gmx_bgzf_member m;
-    size_t next;
-    if (!bgzf_member_at(in, size, at, &m, &next)) return 1;
-    if (m.isize) members.push_back(m);
-    at = next;
-  }
-  uint64_t kMembers = device_feed_members();
-  uint64_t file_text = 0;
-  for (const auto &m : members) file_text += m.isize;
-  while (g_more_feeds.size() + 1 < N) g_more_feeds.emplace_back(new DeviceFeed());
-  auto feed = [&](size_t k) -> DeviceFeed & { return k == 0 ? g_device_feed : *g_more_feeds[k - 1]; };
-  for (size_t k = 0; k < N; ++k) {
-    device_feed_prepare(devs[k], device_feed_text_for(file_text), 0, &feed(k));
-    if (!feed(k).ing) return 1;
-    GMX_CHECK(gmx_ingest_reset(feed(k).ing));
-    GMX_CHECK(gmx_ingest_set_format(feed(k).ing, g_reads_format));
-  }
-  feed_trace("ingests of all engines ready");
-  const uint64_t max_text = gmx_ingest_max_text(feed(0).ing), max_comp = gmx_ingest_max_compressed(feed(0).ing);
-  kMembers = std::min<uint64_t>(kMembers, gmx_ingest_max_members(feed(0).ing));
-  struct Chunk {
-    size_t first, count, lo, hi;
-  };
-  std::vector<Chunk> chunks;
-  for (size_t i = 0; i < members.size();) {
-    Chunk c{i, 0, (size_t)members[i].offset, 0};
-    uint64_t text = 0;
-    while (i < members.size() && c.count < kMembers && text + members[i].isize <= max_text && members[i].offset + members[i].size - c.lo <= max_comp) {
-      text += members[i].isize;
-      c.hi = (size_t)(members[i].offset + members[i].size);
-      ++c.count;
-      ++i;
-    }
-    if (c.count == 0) return 1;
-    chunks.push_back(c);
-  }
-  if (chunks.empty()) return 0;
-  const unsigned T = (unsigned)std::max(1, std::min(threads, 64));
-  std::vector<gmx_bgzf_member> rel;
-  auto dev_of = [&](size_t ci) { return ci % N; };
-  auto slot_of = [&](size_t ci) { return (int)((ci / N) & 1); };
-  auto submit = [&](size_t ci) {  // upload + inflate; the scan follows when the chunk before has been scanned
-    const Chunk &c = chunks[ci];
-    HostBuf<uint8_t> &st = feed(dev_of(ci)).stage[slot_of(ci)];
-    const size_t n = c.hi - c.lo;
-    st.resize(n + 64);
-    parallel_for(T, [&](unsigned t) {
-      const size_t a = n * t / T, b = n * (t + 1) / T;
-      if (b > a) memcpy(st.data() + a, in + c.lo + a, b - a);
-    });
-    rel.assign(members.begin() + (long)c.first, members.begin() + (long)(c.first + c.count));
-    for (auto &m : rel) m.offset -= c.lo;
-    GMX_CHECK(gmx_ingest_submit_bgzf_deferred(feed(dev_of(ci)).ing, slot_of(ci), st.data(), n, rel.data(), rel.size()));
-    feed_trace("chunk submitted to its device (inflate)");
-  };
-  size_t submitted = 0;
-  for (; submitted < std::min(chunks.size(), 2 * N); ++submitted) submit(submitted);
-  std::vector<uint8_t> tail;
-  for (size_t ci = 0; ci < chunks.size(); ++ci) {
-    gmx_ingest *ing = feed(dev_of(ci)).ing;
-    GMX_CHECK(gmx_ingest_scan(ing, slot_of(ci), tail.data(), tail.size(), ci + 1 == chunks.size() ? 1 : 0));
-    gmx_ingest_result res;
-    GMX_CHECK(gmx_ingest_wait(ing, slot_of(ci), &res));
-    feed_trace("chunk scanned");
-    if (const char *tf = getenv("GMX_INGEST_TEST_FAIL_CHUNK"))
-      if ((size_t)atoll(tf) == ci) res.status |= GMX_INGEST_BAD_MEMBER;
-    if (res.status) {
-      for (size_t cj = ci + 1; cj < submitted; ++cj) {  // (chunks inflating ahead: scanned with nothing and dropped, so that their slots are free again)
-        gmx_ingest_result drop;
-        GMX_CHECK(gmx_ingest_scan(feed(dev_of(cj)).ing, slot_of(cj), nullptr, 0, 0));
-        GMX_CHECK(gmx_ingest_wait(feed(dev_of(cj)).ing, slot_of(cj), &drop));
-      }
-      const bool decoder = (res.status & (GMX_INGEST_BAD_MEMBER | GMX_INGEST_BAD_CRC | GMX_INGEST_TOO_MANY_LINES)) != 0;
-      if (!decoder) {
-        if (*delivered == 0) return 1;
-        if (g_reads_format != GMX_INGEST_FORMAT_FASTQ) return 2;
-        die("gram: " + path + ": irregular FASTQ record after the first " + std::to_string(*delivered) +
-            " reads (multi-line or blank lines); decompress and reformat, or use a four-line FASTQ");
-      }
-      return *delivered == 0 && !(res.status & (GMX_INGEST_BAD_MEMBER | GMX_INGEST_BAD_CRC)) ? 1 : 2;
-    }
-    tail.resize(res.tail_bytes);
-    if (res.tail_bytes && gmx_ingest_fetch_tail(ing, slot_of(ci), tail.data(), tail.size()) < 0) die(std::string("gram: ") + gmx_last_error());
-    on_chunk(res, dev_of(ci), slot_of(ci));
-    *delivered += res.n_reads;
-    if (submitted < chunks.size()) submit(submitted++);  // (its slot: chunk submitted - 2 N, waited for and handed on two rounds ago)
-  }
-  return 0;
-}
-
-// ---- plain (uncompressed) four-line FASTQ through the same device chain (round 6) -----------------------------------------
-// The reference reads every text format through one host reader (include/sequence_read/seqread.hpp:94-180, seq_file.h:626-633,
-// quasimap.cpp:65-76). Until round 6 `gram` took the device route for BGZF only and parsed a plain FASTQ on the host: 42 M
-// reads/s parse + map at configs[1], 3.5 x slower than the same reads bgzipped. Now the file's bytes go up as they are: all
-// threads pread their slices of a chunk from the page cache into page-locked memory (ONE pass over the text on the host, no
-// parsing), the chunk is uploaded (gmx_ingest_submit_text) and gmx_nl_* / gmx_records / gmx_fq_pack find the records and pack the
-// bases in HBM; a record cut by a chunk's end is carried into the next chunk on the device. Bound: the host link at ~316 B per
-// 150-base read (measured 120-140 M reads/s; the link's 55 GB/s would be 175 M). Whether a file takes this route or the host parser:
-// plain_fastq_on_device() below. Return values as ingest_bgzf_file.
-// Which reader takes a plain FASTQ (measured on the GPU boxes, configs[1], 4 M x 150 bp = 1.26 GB in the page cache, parse + map;
-// profiles/round6/cli_text_feed_by_threads.txt): the device route moves 316 B per read over the host link and is bound by it —
-// 28-33 ms = 120-140 M reads/s from 2 host threads on, 67 M with ONE (one core copies 21 GB/s out of the page cache) — while the
-// host parser sends 40 B per read and scales with the cores: 24 M reads/s on 1 thread, 35-45 M on 2-4, 52-82 M on 8, 75-102 M on 16,
-// 140-165 M on 32, 140-215 M on 64. So: the device route below 32 host threads (`--max_threads` defaults to 1 in the reference's
-// front-end: 2.8 x), the host parser from 32 threads on. GMX_DEVICE_FASTQ=1 / GMX_HOST_FASTQ=1 force either.
-static bool plain_fastq_on_device(int max_threads, size_t n_engines) {
-  if (getenv("GMX_HOST_FASTQ")) return false;
-  // FASTA / one read per line: no parallel host parser exists for them (parse_fastq_file declines), the alternative is the
-  // general reader on ONE thread: the device route at every thread count
-  if (g_reads_format != GMX_INGEST_FORMAT_FASTQ) return true;
-  if (const char *e = getenv("GMX_DEVICE_FASTQ")) return atoi(e) != 0;
-  (void)n_engines;  // (several engines: the same rule — the chunks are then dealt over the engines' ingests, ingest_text_file_dealt; measured
-                    //  only with several engines on ONE GPU, tools/feed_x8.py, where it has nothing to gain)
-  return max_threads < 32;
-}
-static uint64_t device_feed_text_chunk(size_t scale = 0) {
-  uint64_t c = (128ull << 20) * (scale ? scale : std::min<size_t>(g_block_scale, 4));  // (nested PRGs: larger launches, see g_block_scale; 128 MB: 29-33 ms per 1.26 GB where 64 MB chunks take 34-40)
-  if (const char *e = getenv("GMX_TEXT_CHUNK")) c = std::max<uint64_t>(64, (uint64_t)atoll(e));
-  return std::min<uint64_t>(c, (3ull << 30) - (1u << 20));
-}
-static uint64_t fstat_ok_size(const std::string &path) {
-  struct stat sb;
-  return stat(path.c_str(), &sb) == 0 && S_ISREG(sb.st_mode) ? (uint64_t)sb.st_size : 0;
-}
-static bool looks_like_plain_fastq(const std::string &path, uint64_t *size_out) {
-  const int fd = open(path.c_str(), O_RDONLY);
-  if (fd < 0) return false;
-  struct stat sb;
-  unsigned char h[2] = {0, 0};
-  // (FASTA / one read per line, as detect_reads_format found: any first byte — blank lines may lead — but gzip's)
-  const bool ok = fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size >= 4 && pread(fd, h, 2, 0) == 2 &&
-                  (g_reads_format == GMX_INGEST_FORMAT_FASTQ ? h[0] == '@' : !(h[0] == 0x1f && h[1] == 0x8b));
-  close(fd);
-  if (ok && size_out) *size_out = (uint64_t)sb.st_size;
-  return ok;
-}
-// bytes [at, at + n) of the file into dst, every thread its slice (page cache -> page-locked memory); false: a read failed
-static bool pread_parallel(int fd, uint64_t at, uint8_t *dst, size_t n, unsigned T) {
-  std::atomic<bool> bad{false};
-  parallel_for(T, [&](unsigned t) {
-    size_t lo = n * t / T;
-    const size_t hi = n * (t + 1) / T;
-    while (lo < hi) {
-      const ssize_t got = pread(fd, dst + lo, hi - lo, (off_t)(at + lo));
-      if (got <= 0) {
-        bad.store(true);
-        return;
-      }
-      lo += (size_t)got;
-    }
-  });
-  return !bad.load();
-}
-struct FdCloser {
-  int fd;
-  ~FdCloser() {
-    if (fd >= 0) close(fd);
-  }
-};
-// what a chunk's status means for the caller (both text feeds): 0 go on, else the function's return value
-static int text_chunk_verdict(const gmx_ingest_result &res, const std::string &path, uint64_t delivered) {
-  if (!res.status) return 0;
-  if (res.status & GMX_INGEST_BAD_RECORD) {  // not four-line FASTQ: the host's fast path would say the same
-    if (delivered == 0) return 1;
-    if (g_reads_format != GMX_INGEST_FORMAT_FASTQ) return 2;  // (FASTA / one read per line: the general reader takes over and skips what was mapped)
-    die("gram: " + path + ": irregular FASTQ record after the first " + std::to_string(delivered) +
-        " reads (multi-line or blank lines); reformat, or use a four-line FASTQ");
-  }
-  return delivered == 0 ? 1 : 2;  // lines of a few bytes (more records than the ingest has room for): the host reader's
-}
-
-template <class OnChunk>
-int ingest_text_file(const std::string &path, int threads, int device, OnChunk on_chunk, uint64_t *delivered) {
-  *delivered = 0;
-  uint64_t size = 0;
-  if (!looks_like_plain_fastq(path, &size)) return 1;
-  FdCloser f{open(path.c_str(), O_RDONLY)};
-  if (f.fd < 0) return 1;
-  const uint64_t chunk = std::min<uint64_t>(device_feed_text_chunk(), size);
-  DeviceFeed &df = g_device_feed;
-  device_feed_prepare(device, std::max<uint64_t>(chunk, 1u << 16) + (1u << 16), 0);
-  if (!df.ing) return 1;
-  gmx_ingest *ing = df.ing;
-  GMX_CHECK(gmx_ingest_reset(ing));
-  GMX_CHECK(gmx_ingest_set_format(ing, g_reads_format));
-  const unsigned T = (unsigned)std::max(1, std::min(threads, 64));
-  const size_t n_chunks = (size_t)((size + chunk - 1) / chunk);
-  auto bytes_of = [&](size_t ci) { return (size_t)std::min<uint64_t>(chunk, size - (uint64_t)ci * chunk); };
-  // A thread of its own reads the chunks ahead into four page-locked buffers (round 6: read, submit, wait and map in turn on one
-  // thread cost 1.55 ms per 64 MB chunk of which 1.25 were the read — the reads now run back to back). Buffer k % 4 is free for
-  // chunk k once chunk k - 4 has been waited for (its upload is over).
-  constexpr size_t NB = 4;
-  HostBuf<uint8_t> *const ring = df.stage;  // (sized beside the index load: device_feed_prepare; page-locking 4 x 64 MB takes 30 ms)
-  struct Reader {
-    std::mutex m;
-    std::condition_variable cv;
-    size_t staged = 0, waited = 0;  // chunks read so far / chunks the consumer is done with
-    bool failed = false, stop = false;
-    std::thread th;
-    ~Reader() {
-      {
-        std::lock_guard<std::mutex> lk(m);
-        stop = true;
-      }
-      cv.notify_all();
-      if (th.joinable()) th.join();
-    }
-  } rd;
-  for (size_t b = 0; b < std::min(NB, n_chunks); ++b) ring[b].resize(bytes_of(0) + 64);
-  rd.th = std::thread([&]() {
-    for (size_t k = 0; k < n_chunks; ++k) {
-      {
-        std::unique_lock<std::mutex> lk(rd.m);
-        rd.cv.wait(lk, [&] { return rd.stop || k < rd.waited + NB; });
-        if (rd.stop) return;
-      }
-      const double t_read = now_s();
-      const bool ok = pread_parallel(f.fd, (uint64_t)k * chunk, ring[k % NB].data(), bytes_of(k), T);
-      g_feed.read_s += now_s() - t_read;
-      feed_trace("  text chunk read into page-locked memory");
-      {
-        std::lock_guard<std::mutex> lk(rd.m);
-        if (!ok) rd.failed = true;
-        rd.staged = k + 1;
-      }
-      rd.cv.notify_all();
-      if (!ok) return;
-    }
-  });
-  auto staged = [&](size_t k, bool block) -> int {  // 1: chunk k is read, 0: not yet (block = false), -1: its read failed
-    std::unique_lock<std::mutex> lk(rd.m);
-    if (block) rd.cv.wait(lk, [&] { return rd.staged > k || rd.failed; });
-    if (rd.staged > k) return 1;
-    return rd.failed ? -1 : 0;
-  };
-  size_t n_submitted = 0;
-  auto submit = [&]() {
-    const size_t ci = n_submitted;
-    GMX_CHECK(gmx_ingest_submit_text(ing, (int)(ci % 3), ring[ci % NB].data(), bytes_of(ci), ci + 1 == n_chunks ? 1 : 0));
-    ++n_submitted;
-    feed_trace("text chunk submitted to the device");
-  };
-  bool io_error = false;
-  for (size_t ci = 0; ci < n_chunks && !io_error; ++ci) {
-    if (n_submitted <= ci) {  // this chunk itself: wait for its bytes
-      if (staged(ci, true) < 0) {
-        io_error = true;
-        break;
-      }
-      submit();
-    }
-    while (n_submitted < std::min(n_chunks, ci + 3) && staged(n_submitted, false) == 1) submit();  // the two behind it, when they are there
-    gmx_ingest_result res;
-    GMX_CHECK(gmx_ingest_wait(ing, (int)(ci % 3), &res));
-    feed_trace("text chunk scanned and packed");
-    if (const char *tf = getenv("GMX_INGEST_TEST_FAIL_CHUNK"))  // test hook: "more records than the ingest has room for" in this chunk
-      if ((size_t)atoll(tf) == ci) res.status |= GMX_INGEST_TOO_MANY_LINES;
-    if (res.status) {
-      for (size_t cj = ci + 1; cj < n_submitted; ++cj) {  // (the chunks behind are in flight: let them finish before the slots are reused)
-        gmx_ingest_result drop;
-        GMX_CHECK(gmx_ingest_wait(ing, (int)(cj % 3), &drop));
-      }
-      return text_chunk_verdict(res, path, *delivered);
-    }
-    on_chunk(res, (int)(ci % 3));
-    *delivered += res.n_reads;
-    {
-      std::lock_guard<std::mutex> lk(rd.m);
-      rd.waited = ci + 1;
-    }
-    rd.cv.notify_all();
-  }
-  if (io_error) {  // (chunks in flight first; then the host reader reports the file)
-    for (size_t cj = 0; cj < n_submitted; ++cj) {
-      gmx_ingest_result drop;
-      (void)gmx_ingest_wait(ing, (int)(cj % 3), &drop);
-    }
-    return *delivered == 0 ? 1 : 2;
-  }
-  return 0;
-}
-
-// A PLAIN gzip file (one deflate stream per member: gzip, pigz, ENA / SRA downloads) decoded on the device
-// (gmx_ingest_submit_gzip): chunks of GMX_GZ_CHUNK compressed bytes (default 32 MB) with 1 MB of the file behind
-// each as look-ahead, read into page-locked buffers and submitted with two chunks on the device. One engine only: the deflate
-// stream's window and position live in that engine's ingest. Return values as ingest_bgzf_file (1: not gzip).
-static uint64_t device_feed_gz_chunk() {
-  uint64_t c = 32ull << 20;
-  if (const char *e = getenv("GMX_GZ_CHUNK")) c = std::max<uint64_t>(64, (uint64_t)atoll(e));
-  return std::min<uint64_t>(c, 256ull << 20);
-}
-static bool looks_like_gzip(const std::string &path, uint64_t *size_out) {
-  const int fd = open(path.c_str(), O_RDONLY);
-  if (fd < 0) return false;
-  struct stat sb;
-  unsigned char h[3] = {0, 0, 0};
-  const bool ok = fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size >= 18 && pread(fd, h, 3, 0) == 3 && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8;
-  close(fd);
-  if (ok && size_out) *size_out = (uint64_t)sb.st_size;
-  return ok;
-}
-
-template <class OnChunk>
-int ingest_gzip_file(const std::string &path, int threads, int device, OnChunk on_chunk, uint64_t *delivered) {
-  *delivered = 0;
-  uint64_t size = 0;
-  if (!looks_like_gzip(path, &size)) return 1;
-  FdCloser f{open(path.c_str(), O_RDONLY)};
-  if (f.fd < 0) return 1;
-  const uint64_t chunk = std::min<uint64_t>(device_feed_gz_chunk(), size), look = 1u << 20;
-  DeviceFeed &df = g_device_feed;
-  // text room for 8:1 (FASTQ compresses 3-5 fold; a chunk that inflates further comes back with GMX_INGEST_GZ_TEXT_LIMIT)
-  device_feed_prepare(device, std::max<uint64_t>(2 * (chunk + look), std::min<uint64_t>(8 * chunk, 3ull << 30)), chunk + look + 64);
-  if (!df.ing || gmx_ingest_max_compressed(df.ing) < chunk + look) return 1;
-  gmx_ingest *ing = df.ing;
-  GMX_CHECK(gmx_ingest_reset(ing));
-  GMX_CHECK(gmx_ingest_set_format(ing, g_reads_format));
-  const unsigned T = (unsigned)std::max(1, std::min(threads, 64));
-  const size_t n_chunks = (size_t)((size + chunk - 1) / chunk);
-  auto fail_chunk = [&]() -> size_t {
-    const char *tf = getenv("GMX_INGEST_TEST_FAIL_CHUNK");  // test hook: the device decoder "gives up" on this chunk
-    return tf ? (size_t)atoll(tf) : ~(size_t)0;
-  };
-  size_t n_submitted = 0;
-  auto submit = [&]() -> bool {
-    const size_t ci = n_submitted;
-    const uint64_t at = (uint64_t)ci * chunk, own = std::min<uint64_t>(chunk, size - at);
-    const bool final_chunk = ci + 1 == n_chunks;
-    const uint64_t n = final_chunk ? own : std::min<uint64_t>(own + look, size - at);
-    const double t_read = now_s();
-    if (!pread_parallel(f.fd, at, df.stage[ci % 3].data(), (size_t)n, T)) return false;
-    g_feed.read_s += now_s() - t_read;
-    GMX_CHECK(gmx_ingest_submit_gzip(ing, (int)(ci % 3), df.stage[ci % 3].data(), n, own, final_chunk ? 1 : 0));
-    ++n_submitted;
-    feed_trace("gzip chunk submitted to the device");
-    return true;
-  };
-  auto drain = [&](size_t from) {
-    for (size_t cj = from; cj < n_submitted; ++cj) {
-      gmx_ingest_result drop;
-      (void)gmx_ingest_wait(ing, (int)(cj % 3), &drop);
-    }
-  };
-  for (size_t ci = 0; ci < n_chunks; ++ci) {
-    while (n_submitted < std::min(n_chunks, ci + 2)) {  // this chunk and the one behind it on the device
-      if (!submit()) {
-        drain(ci);
-        return *delivered == 0 ? 1 : 2;
-      }
-    }
-    gmx_ingest_result res;
-    GMX_CHECK(gmx_ingest_wait(ing, (int)(ci % 3), &res));
-    feed_trace("gzip chunk decoded, scanned and packed");
-    if (ci == fail_chunk()) res.status |= GMX_INGEST_BAD_MEMBER;
-    if (res.status) {
-      drain(ci + 1);
-      return 2;  // (gave up, also on its first chunk: the host reader takes the file over and reports real damage itself)
-    }
-    on_chunk(res, (int)(ci % 3));
-    *delivered += res.n_reads;
-  }
-  return 0;
-}
-
-// Several engines: the chunks dealt round, each uploaded to its device at once (gmx_ingest_submit_text_deferred, two per device
-// ahead), scanned in file order with the cut record of the chunk before handed over through the host — as ingest_bgzf_file_dealt.
-template <class OnChunk>
-int ingest_text_file_dealt(const std::string &path, int threads, const std::vector<int> &devs, OnChunk on_chunk, uint64_t *delivered) {
-  *delivered = 0;
-  const size_t N = devs.size();
-  uint64_t size = 0;
-  if (!looks_like_plain_fastq(path, &size)) return 1;
-  FdCloser f{open(path.c_str(), O_RDONLY)};
-  if (f.fd < 0) return 1;
-  // (chunks of 32 MB here — scaled for nested PRGs —: every engine's ingest and its two page-locked buffers are made for the chunk size
-  //  the moment the first plain file arrives — N x (1.1 GB of device memory + 256 MB page-locked) at the single-engine size of 128 MB
-  //  cost a four-engine run 0.25 s before its first read was mapped, tools/cli_dealt_text.sh)
-  const uint64_t chunk = std::min<uint64_t>(getenv("GMX_TEXT_CHUNK") ? device_feed_text_chunk() : device_feed_text_chunk() / 4, size);
-  while (g_more_feeds.size() + 1 < N) g_more_feeds.emplace_back(new DeviceFeed());
-  auto feed = [&](size_t k) -> DeviceFeed & { return k == 0 ? g_device_feed : *g_more_feeds[k - 1]; };
-  for (size_t k = 0; k < N; ++k) {
-    device_feed_prepare(devs[k], std::max<uint64_t>(chunk, 1u << 16) + (1u << 16), 0, &feed(k));
-    if (!feed(k).ing) return 1;
-    GMX_CHECK(gmx_ingest_reset(feed(k).ing));
-    GMX_CHECK(gmx_ingest_set_format(feed(k).ing, g_reads_format));
-  }
-  const size_t n_chunks = (size_t)((size + chunk - 1) / chunk);
-  const unsigned T = (unsigned)std::max(1, std::min(threads, 64));
-  auto dev_of = [&](size_t ci) { return ci % N; };
-  auto slot_of = [&](size_t ci) { return (int)((ci / N) & 1); };
-  bool io_error = false;
-  auto submit = [&](size_t ci) {
-    const uint64_t lo = (uint64_t)ci * chunk;
-    const size_t n = (size_t)std::min<uint64_t>(chunk, size - lo);
-    HostBuf<uint8_t> &st = feed(dev_of(ci)).stage[slot_of(ci)];
-    st.resize(n + 64);
-    if (!pread_parallel(f.fd, lo, st.data(), n, T)) io_error = true;
-    GMX_CHECK(gmx_ingest_submit_text_deferred(feed(dev_of(ci)).ing, slot_of(ci), st.data(), n));
-    feed_trace("text chunk submitted to its device");
-  };
-  size_t submitted = 0;
-  for (; submitted < std::min(n_chunks, 2 * N); ++submitted) submit(submitted);
-  std::vector<uint8_t> tail;
-  for (size_t ci = 0; ci < n_chunks; ++ci) {
-    gmx_ingest *ing = feed(dev_of(ci)).ing;
-    GMX_CHECK(gmx_ingest_scan(ing, slot_of(ci), tail.data(), tail.size(), ci + 1 == n_chunks ? 1 : 0));
-    gmx_ingest_result res;
-    GMX_CHECK(gmx_ingest_wait(ing, slot_of(ci), &res));
-    feed_trace("text chunk scanned");
-    if (const char *tf = getenv("GMX_INGEST_TEST_FAIL_CHUNK"))
-      if ((size_t)atoll(tf) == ci) res.status |= GMX_INGEST_TOO_MANY_LINES;
-    if (io_error) res.status |= GMX_INGEST_TOO_MANY_LINES;  // (a failed read: the host reader takes the file and reports it)
-    if (res.status) {
-      for (size_t cj = ci + 1; cj < submitted; ++cj) {  // (chunks uploaded ahead: scanned with nothing and dropped, so that their slots are free again)
-        gmx_ingest_result drop;
-        GMX_CHECK(gmx_ingest_scan(feed(dev_of(cj)).ing, slot_of(cj), nullptr, 0, 0));
-        GMX_CHECK(gmx_ingest_wait(feed(dev_of(cj)).ing, slot_of(cj), &drop));
-      }
-      return text_chunk_verdict(res, path, *delivered);
-    }
-    tail.resize(res.tail_bytes);
-    if (res.tail_bytes && gmx_ingest_fetch_tail(ing, slot_of(ci), tail.data(), tail.size()) < 0) die(std::string("gram: ") + gmx_last_error());
-    on_chunk(res, dev_of(ci), slot_of(ci));
-    *delivered += res.n_reads;
-    if (submitted < n_chunks) submit(submitted++);
-  }
-  return 0;
-}
+#include "gram_device_feed.h"  // the device feed: reads files decoded, scanned and packed on the GPU
 
 struct ReadStats {  // include/genotype/read_stats.hpp
   double mean_cov_depth = -1, variance_cov_depth = -1;
@@ -1865,7 +1177,7 @@ int run_parse_check(const std::string &path, int threads) {
     fast = Flat{};
     ParsedReads blk;
     uint64_t delivered = 0;
-    auto take = [&](const gmx_ingest_result &res, int slot) {
+    auto take = [&](const gmx_ingest_result &res, size_t, int slot) {
       blk.reset();
       blk.n_reads = res.n_reads;
       blk.n_bases = res.n_bases;
@@ -1879,9 +1191,8 @@ int run_parse_check(const std::string &path, int threads) {
     // ("any": the format detected and set as `gram genotype` does; else four-line FASTQ only, as before the other scanners existed)
     g_reads_format = std::string(getenv("GMX_PARSE_CHECK_DEVICE")) == "any" ? detect_reads_format(path) : GMX_INGEST_FORMAT_FASTQ;
     const bool dev_bam = g_reads_format == GMX_INGEST_FORMAT_BAM;  // (BAM: BGZF or nothing)
-    int rc = ingest_bgzf_file(path, threads, 0, take, &delivered);
-    if (rc == 1 && delivered == 0 && !dev_bam) rc = ingest_gzip_file(path, threads, 0, take, &delivered);  // (plain gzip: pieces decoded side by side)
-    if (rc == 1 && delivered == 0 && !dev_bam) rc = ingest_text_file(path, threads, 0, take, &delivered);  // (not BGZF: plain text through the same kernels)
+    FeedRoute ran;
+    const int rc = ingest_reads_file(path, threads, {0}, false, !dev_bam, !dev_bam, take, &delivered, &ran);
     if (rc == 0)
       std::cout << "device " << fast.offsets.size() - 1 << " " << fast.bases.size() << " " << fnv(fast) << std::endl;
     else
@@ -2138,14 +1449,14 @@ int run_genotype(const Args &a) {
         if (fd < 0) break;
         const bool bg = pread(fd, h, 16, 0) == 16 && fstat(fd, &sb) == 0 && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && h[3] == 4 && h[12] == 'B' && h[13] == 'C';
         close(fd);
-        if (bg && hipSetDeviceForPrewarm(devices[0])) {
+        if (bg) {
           const uint64_t text = device_feed_text_for((uint64_t)sb.st_size * 6);
           device_feed_prepare(devices[0], text, std::min<uint64_t>((uint64_t)sb.st_size, text / 2) + 64);
         } else if (!(h[0] == 0x1f && h[1] == 0x8b) && fstat_ok_size(smp.reads[0]) >= 4) {  // plain FASTQ / FASTA / one read per line: text chunks (ingest_text_file)
           g_reads_format = detect_reads_format(smp.reads[0]);  // (the files' loop sets it again; nothing reads it in between)
           if ((g_reads_format == GMX_INGEST_FORMAT_FASTQ && h[0] != '@') || !plain_fastq_on_device(max_threads, devices.size())) break;
           const uint64_t chunk = std::min<uint64_t>(device_feed_text_chunk(1), fstat_ok_size(smp.reads[0]));  // (a nested PRG's larger chunks: sized when the file is opened)
-          device_feed_prepare(devices[0], std::max<uint64_t>(chunk, 1u << 16) + (1u << 16), chunk + 64);
+          device_feed_prepare(devices[0], device_feed_text_room(chunk), chunk + 64);
         }
         break;
       }
@@ -2318,7 +1629,7 @@ int run_genotype(const Args &a) {
     // A BGZF file is decoded on the GPU (GMX_HOST_GZ=1: on the host as before): compressed members up, reads found and packed in
     // HBM, mapped where they lie. Should the device decoder give up on a chunk, the host reader below takes the file from its
     // start and drops the reads already mapped. With several engines the file's chunks are dealt round: every GPU decodes and maps
-    // its share (ingest_bgzf_file_dealt), the record a chunk's end cuts travels to the next GPU through the host.
+    // its share (feed_chunks_dealt), the record a chunk's end cuts travels to the next GPU through the host.
     uint64_t skip_reads = 0;
     g_reads_format = GMX_INGEST_FORMAT_FASTQ;
     // (every file's format is looked at, whatever the route: a .sam, a .cram or a .bam that is none ends the run here)
@@ -2360,22 +1671,17 @@ int run_genotype(const Args &a) {
         }
         feed_trace("  chunk handed to the engine");
         // (the slot's planes are read by the launch just enqueued: on the engine's NULL stream or on its second workspace's stream)
-        GMX_CHECK(gmx_ingest_release_after(k == 0 ? g_device_feed.ing : g_more_feeds[k - 1]->ing, slot, nullptr));
-        if (void *second = gmx_engine_second_stream(ek)) GMX_CHECK(gmx_ingest_release_after(k == 0 ? g_device_feed.ing : g_more_feeds[k - 1]->ing, slot, second));
+        GMX_CHECK(gmx_ingest_release_after(device_feed(k).ing, slot, nullptr));
+        if (void *second = gmx_engine_second_stream(ek)) GMX_CHECK(gmx_ingest_release_after(device_feed(k).ing, slot, second));
         in_file += n;
         total_reads += n;
       };
-      int rc = dealt ? ingest_bgzf_file_dealt(path, max_threads, devices, map_chunk, &delivered)
-                     : ingest_bgzf_file(path, max_threads, devices[0], [&](const gmx_ingest_result &res, int slot) { map_chunk(res, 0, slot); }, &delivered);
-      // plain gzip, one engine: decoded on the device too, at any --max_threads (the host's inflation is the
-      // slower at every thread count); several engines keep the host reader (the stream's window would travel through the host)
-      const bool gz_route = rc == 1 && delivered == 0 && !is_bam && devices.size() == 1 && looks_like_gzip(path, nullptr);
-      if (gz_route) rc = ingest_gzip_file(path, max_threads, devices[0], [&](const gmx_ingest_result &res, int slot) { map_chunk(res, 0, slot); }, &delivered);
-      // not BGZF: plain four-line FASTQ takes the same route minus the inflate kernel (round 6; GMX_HOST_FASTQ=1: the host parser)
-      const bool text_route = rc == 1 && delivered == 0 && !is_bam && !gz_route && plain_fastq_on_device(max_threads, devices.size());
-      if (text_route)
-        rc = dealt ? ingest_text_file_dealt(path, max_threads, devices, map_chunk, &delivered)
-                   : ingest_text_file(path, max_threads, devices[0], [&](const gmx_ingest_result &res, int slot) { map_chunk(res, 0, slot); }, &delivered);
+      // BGZF, else plain gzip — one engine: decoded on the device too, at any --max_threads (the host's inflation is
+      // the slower at every thread count); several engines keep the host reader —, else plain text: four-line FASTQ takes the same
+      // route minus the inflate kernel (round 6; GMX_HOST_FASTQ=1: the host parser)
+      FeedRoute ran;
+      const int rc = ingest_reads_file(path, max_threads, devices, dealt, !is_bam && devices.size() == 1, !is_bam && plain_fastq_on_device(max_threads, devices.size()),
+                                       map_chunk, &delivered, &ran);
       auto sync_all = [&]() {
         for (int d = 0; d < (dealt ? gmx_group_size(grp) : 1); ++d) GMX_CHECK(gmx_engine_sync(gmx_group_engine(grp, d)));
       };
@@ -2386,7 +1692,7 @@ int run_genotype(const Args &a) {
       }
       if (rc == 2) {
         sync_all();
-        std::cerr << "warning: " << path << ": the device-side " << (text_route || is_bam ? reads_format_scanner() : gz_route ? "gzip decoder" : "BGZF decoder") << " gave up after " << delivered << " reads; the host reader takes over" << std::endl;
+        std::cerr << "warning: " << path << ": the device-side " << (ran == FeedRoute::Text || is_bam ? reads_format_scanner() : ran == FeedRoute::Gzip ? "gzip decoder" : "BGZF decoder") << " gave up after " << delivered << " reads; the host reader takes over" << std::endl;
         skip_reads = delivered;
         in_file = 0;               // (the host reader counts the file's reads from its start again)
         total_reads -= delivered;

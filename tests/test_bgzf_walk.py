@@ -1,5 +1,5 @@
 """The BGZF member walk on the host (gramtools_amd.bgzf_members: what `gram` does before it hands a file to the device-side
-decoder, gram_main.cpp: bgzf_member_at): offsets, sizes and trailers of the members without inflating anything (SAM spec 4.1).
+decoder, gram_device_feed.h: bgzf_member_at): offsets, sizes and trailers of the members without inflating anything (SAM spec 4.1).
 No GPU needed."""
 import gzip
 import struct
