@@ -165,6 +165,8 @@ SYMBOLS = {
     "gmx_engine_position_count": (_i64, [_vp]),
     "gmx_engine_fetch_positions": (C.c_int, [_vp, _u64, _u64, _u32p]),
     "gmx_engine_record_strands": (C.c_int, [_vp, C.c_int]),
+    "gmx_engine_set_max_candidates": (C.c_int, [_vp, C.c_uint32]),
+    "gmx_engine_max_candidates": (C.c_uint32, [_vp]),
     "gmx_coverage_fetch_strand": (C.c_int, [_vp, C.c_int, _u32p, _u32p, _u32p]),
     "gmx_coverage_fetch_grouped_log_strand": (_i64, [_vp, C.c_int, _u32p, _u64]),
     "gmx_coverage_export_grouped_log": (_i64, [_vp, _u32p, _u64]),
@@ -203,6 +205,7 @@ SYMBOLS = {
     "gmx_group_position_count": (_i64, [_vp]),
     "gmx_group_fetch_positions": (C.c_int, [_vp, _u64, _u64, _u32p]),
     "gmx_group_record_strands": (C.c_int, [_vp, C.c_int]),
+    "gmx_group_set_max_candidates": (C.c_int, [_vp, C.c_uint32]),
     "gmx_comm_unique_id": (C.c_int, [_u8p]),
     "gmx_comm_create": (C.c_int, [_u8p, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),
     "gmx_comm_destroy": (None, [_vp]),

@@ -1188,17 +1188,25 @@ struct GmxWhere {
   uint32_t pos, n;
   bool on;
 };
+// gmx_cover_task's drawn_from for a task left out by the limit on candidates (more than one candidate by definition, so the
+// value is also "> 1"; a real range cannot reach it: it is bounded by the instances a scratch holds)
+#define GMX_DRAWN_LEFT_OUT 0x80000000u
 
 // ---------------------------------------------------------------------------
 // The whole recording step for one mapped task.
 // ---------------------------------------------------------------------------
 template <class Env>
 GMX_HD void gmx_cover_task(const GmxIndexView &ix, Env &env, const GmxFinalState *finals, uint32_t n_final,
-                           uint32_t read_len, uint32_t seed, int rng_mode, uint32_t *drawn_from = nullptr, GmxWhere *where = nullptr) {
-  // drawn_from (optional): how many mapping instances the selection drew from (0: it did not draw)
+                           uint32_t read_len, uint32_t seed, int rng_mode, uint32_t *drawn_from = nullptr, GmxWhere *where = nullptr,
+                           uint32_t limit = 0) {
+  // drawn_from (optional): how many mapping instances the selection drew from (0: it did not draw), or GMX_DRAWN_LEFT_OUT: the
+  //   selection had more candidates than `limit` and the task was left out
+  // limit (0: none; gmx_engine_set_max_candidates): a task whose selection has a class and more than `limit`
+  //   candidates (non-variant instances + classes: the draw's range) makes no draw and records nothing; it stays GMX_TASK_MAPPED
   // where (optional; filled when where->on): the task's position record, valid when the task ends with env.status ==
   //   GMX_TASK_MAPPED — pos: the smallest PRG position among the instances the selection chose from (all of them when there is
-  //   no class, the non-variant ones when the draw fell on them, else those of the drawn class's items), n: gmx_count_instances
+  //   no class or the task is left out, the non-variant ones when the draw fell on them, else those of the drawn class's items),
+  //   n: gmx_count_instances
   const bool want_where = where != nullptr && where->on;
   typedef GmxScratch<Env> S;
   if (n_final == 1 && (finals[0].lo == finals[0].hi || gmx_text_form(finals[0].hi))) {
@@ -1289,6 +1297,19 @@ GMX_HD void gmx_cover_task(const GmxIndexView &ix, Env &env, const GmxFinalState
     if (gmx_key_cmp(env, env.sget(ord + i - 1), env.sget(ord + i)) != 0) ++n_classes;
   // --- selection (random_select_entry, coverage_common.cpp:95-108) ---
   uint32_t total = nonvariant + n_classes;
+  if (limit && total > limit) {  // left out: no draw, nothing recorded, nothing reserved (the classes are complete: every tier decides alike)
+    if (drawn_from) *drawn_from = GMX_DRAWN_LEFT_OUT;
+    if (want_where) {  // nothing drawn: all its instances, as with no class (where->pos holds the non-variant ones' minimum)
+      uint32_t m = where->pos;
+      for (uint32_t it = 0; it < n_items; ++it) {
+        const uint32_t b = S::items + it * S::ITEM_W;
+        const uint32_t p = gmx_min_occ_pos(ix, env.sget(b), env.sget(b + 1));
+        m = p < m ? p : m;
+      }
+      where->pos = m;
+    }
+    return;
+  }
   uint32_t r;
   if (!gmx_uniform_1_to_n(seed, total, rng_mode, r)) {
     env.fail(GMX_TASK_ERROR);

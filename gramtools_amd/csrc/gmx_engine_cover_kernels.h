@@ -13,6 +13,7 @@ struct CoverAcc {
   uint32_t *scratch_big;
   uint32_t n_lanes_big;
   int rng_mode;
+  uint32_t max_candidates;  // the limit on a selection's candidates (gmx_engine_set_max_candidates; 0: none)
   uint32_t log_sites;   // the index has sites with more than 8 alleles (users of the log)
   uint32_t *heap;       // the last tier's memory (gmx_tail_stage)
   uint64_t heap_words;
@@ -329,7 +330,7 @@ __device__ uint32_t gmx_tail_item(const GmxIndexView &ix, const BatchView &b, co
   env.log_at = 0;
   uint32_t drawn_from = 0;
   GmxWhere where{0u, 0u, o.positions != nullptr};
-  gmx_cover_task(ix, env, finals, nf, len, b.seeds[task >> 1], acc.rng_mode, &drawn_from, &where);
+  gmx_cover_task(ix, env, finals, nf, len, b.seeds[task >> 1], acc.rng_mode, &drawn_from, &where, acc.max_candidates);
   env.log_abandon();
   if (o.positions && env.status == GMX_TASK_MAPPED) gmx_position_put(o, task, where.pos, where.n);
   if (env.status == GMX_TASK_MAPPED && is_search) {
@@ -337,7 +338,7 @@ __device__ uint32_t gmx_tail_item(const GmxIndexView &ix, const BatchView &b, co
     if (o.outcomes) gmx_outcome_put(o, task, GMX_OUTCOME_MAPPED);
     o.n_final[task] = nf;
   }
-  if (o.outcomes && env.status == GMX_TASK_MAPPED && drawn_from > 1u) gmx_outcome_multi(o, task);
+  if (o.outcomes && env.status == GMX_TASK_MAPPED && drawn_from > 1u) gmx_outcome_selection(o, task, drawn_from);
   return env.status;
 }
 
@@ -462,10 +463,10 @@ __global__ void __launch_bounds__(GMX_BLOCK) gmx_cover_kernel(GmxIndexView ix, B
 #endif
     uint32_t drawn_from = 0;
     GmxWhere where{0u, 0u, o.positions != nullptr};
-    gmx_cover_task(ix, env, finals, nf, len, b.seeds[read], acc.rng_mode, &drawn_from, &where);
+    gmx_cover_task(ix, env, finals, nf, len, b.seeds[read], acc.rng_mode, &drawn_from, &where, acc.max_candidates);
     env.log_abandon();
     if (o.positions && env.status == GMX_TASK_MAPPED) gmx_position_put(o, task, where.pos, where.n);
-    if (o.outcomes && env.status == GMX_TASK_MAPPED && drawn_from > 1u) gmx_outcome_multi(o, task);
+    if (o.outcomes && env.status == GMX_TASK_MAPPED && drawn_from > 1u) gmx_outcome_selection(o, task, drawn_from);
 #ifdef GMX_LOOP_STATS
     env.prof(5);
     t_kernel = env.prof_t;
@@ -609,8 +610,12 @@ __device__ __noinline__ void gmx_coop_position(const uint32_t *sa, uint2 *positi
   if (writer) positions[(base << 1) + task] = make_uint2(mn, n);
 }
 
+// (amdgpu_waves_per_eu(4, 8): the kernel's four waves per SIMD, 128 registers, stated to the register allocator. Without it the
+//  limit on candidates — one more kernel argument to test at the draw — came out at 130 registers and three waves in every form
+//  tried; with it the same code is allocated in 128 without a spill to scratch: profiles/max_candidates/README.md.)
 template <int LIST>
-__global__ void __launch_bounds__(64) gmx_cover_coop_kernel(GmxIndexView ix, BatchView b, SearchOut o, BigOut g, CoverAcc acc) {
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8)))
+gmx_cover_coop_kernel(GmxIndexView ix, BatchView b, SearchOut o, BigOut g, CoverAcc acc) {
   typedef typename CoopSizes<LIST>::Item CoopItemEnv;
   typedef typename CoopSizes<LIST>::Class CoopClassEnv;
   typedef GmxScratch<CoopItemEnv> SI;
@@ -767,7 +772,10 @@ __global__ void __launch_bounds__(64) gmx_cover_coop_kernel(GmxIndexView ix, Bat
     if (have && !rejected && !failed && items16 != 0u) {
       uint32_t r = 0;
       drawn_from = nonvariant + n_classes;
-      if (!gmx_uniform_1_to_n(b.seeds[ts.task >> 1], nonvariant + n_classes, acc.rng_mode, r)) {
+      if (acc.max_candidates && drawn_from > acc.max_candidates) {  // left out: no draw, nothing recorded
+        drawn_from = GMX_DRAWN_LEFT_OUT;
+        member = is_item || nonvar;  // (every instance: candidates of the position record only — the class phase below does not run)
+      } else if (!gmx_uniform_1_to_n(b.seeds[ts.task >> 1], nonvariant + n_classes, acc.rng_mode, r)) {
         err = GMX_TASK_ERROR;
       } else if (r > nonvariant) {
         member = is_item && rank == r - nonvariant - 1u;
@@ -778,14 +786,15 @@ __global__ void __launch_bounds__(64) gmx_cover_coop_kernel(GmxIndexView ix, Bat
     // Written HERE, before the class is merged and recorded — a task that the next phase turns away (class scratch exceeded: the
     // serial instance; log full: the replay) is redone from the same states with the same seed and writes the same record again —
     // from what the lanes left in LDS, and out of line: the kernel's register count, which decides its occupancy, stays what it is
-    // without the recording. Candidates: the drawn class's lanes, or the non-variant lanes (the lump is drawn, or no class at all).
+    // without the recording. Candidates: the drawn class's lanes, or the non-variant lanes (the lump is drawn, or no class at all);
+    // a task that was left out has every item and non-variant lane marked `member` for this call.
     if (o.positions)  // (wave-uniform: every lane takes part in the shuffles)
       gmx_coop_position(ix.sa, o.positions, o.position_base, ts.task, members16 != 0u ? member : nonvar, ie.sget(SI::items + 0),
                         ie.sget(SI::items + 1), ie.sget(SI::hull(ie)), have && gl == 0 && !rejected && !failed && err == 0u);
     GMX_COOP_PHASE(2);
     // --- the drawn class: its first lane merges the members and records ---
     bool class_overflow = false, class_logfull = false;
-    if (member && gl == (uint32_t)__ffs(members16) - 1u) {
+    if (member && drawn_from != GMX_DRAWN_LEFT_OUT && gl == (uint32_t)__ffs(members16) - 1u) {
       const uint32_t read = ts.task >> 1;
       const uint32_t len = read_len(b, read);
       ce.arena = ts.arena;
@@ -843,7 +852,7 @@ __global__ void __launch_bounds__(64) gmx_cover_coop_kernel(GmxIndexView ix, Bat
     if (have && gl == 0 && logfull)
       o.log_retry_list[atomicAdd(&o.counters[GMX_CNT_LOG_RETRY * GMX_CNT_STRIDE], 1u)] = entry;
     if (have && gl == 0 && rejected) reject[atomicAdd(reject_n, 1u)] = entry;
-    if (o.outcomes && have && gl == 0 && !rejected && !logfull && drawn_from > 1u) gmx_outcome_multi(o, ts.task);
+    if (o.outcomes && have && gl == 0 && !rejected && !logfull && drawn_from > 1u) gmx_outcome_selection(o, ts.task, drawn_from);
     if (err != 0u && atomicCAS(&o.error[0], 0u, err) == 0u) o.error[1] = ts.task;
     __syncthreads();  // the scratch is reused by the next round
     GMX_COOP_PHASE(3);

@@ -80,6 +80,9 @@ struct gmx_engine {
   // Coverage per strand (gmx_engine_record_strands): two accumulator blocks of n_acc words, forward tasks' then reverse-complement
   // tasks' (CoverAcc::rev_off = n_acc), the limbs behind both: n_fused = 2 * n_acc + 32. Off: one block, rev_off = 0.
   bool record_strands = false;
+  // The limit on a selection's candidates (gmx_engine_set_max_candidates; 0: none). Like record_strands it changes
+  // only while nothing is recorded, and the twin reads its owner's: a replay or the second workspace meets the first pass's value.
+  uint32_t max_candidates = 0;
   bool recorded = false;  // something may have been added to the block since it was last zeroed (launches, an exchange)
   std::vector<uint32_t> phys_allele, phys_pb, phys_grouped;  // logical slot -> slot of the block (gmx_coverage_fetch)
   std::vector<uint32_t> hit_fix;                             // hit counters and the logical slots they count for
@@ -543,6 +546,8 @@ int gmx_engine_create(const gmx_index *ixh, const gmx_engine_opts *opts_in, gmx_
       *out = nullptr;
       return rc;
     }
+  // MEASUREMENT HOOK ONLY (profiles/max_candidates: the limit's cost in an unchanged benchmark)
+  if (const char *mc = getenv("GMX_MAX_CANDIDATES")) e->max_candidates = (uint32_t)strtoul(mc, nullptr, 10);
   return GMX_OK;
 } GMX_GUARD_INT("gmx_engine_create")
 
@@ -1217,7 +1222,7 @@ static int launch_batch(gmx_engine *e, const BatchInput &in, hipStream_t stream)
   HIP_TRY(hipEventRecord(e->ev_fork, stream));
   HIP_TRY(hipStreamWaitEvent(e->side_stream, e->ev_fork, 0));
   CoverAcc acc{e->d_fused, e->d_log, e->d_log_cursor, e->log_cap, e->d_scratch_big, e->cover_big_lanes, e->opts.rng_mode,
-               e->log_sites ? 1u : 0u, e->d_heap, e->heap_words, e->d_status, (uint32_t)n_reads * 2u, e->d_stats,
+               (e->owner ? e->owner : e)->max_candidates, e->log_sites ? 1u : 0u, e->d_heap, e->heap_words, e->d_status, (uint32_t)n_reads * 2u, e->d_stats,
                (e->owner ? e->owner : e)->record_strands ? (uint32_t)e->n_acc : 0u};
   if (seeded) {  // what gmx_seed_kernel sent to the large-capacity pass (reads in repeats), and its coverage: on side 2
     HIP_TRY(hipStreamWaitEvent(e->side2_stream, e->ev_fork, 0));
@@ -2220,6 +2225,26 @@ int gmx_engine_record_strands(gmx_engine *e, int on) try {
   HIP_TRY(hipDeviceSynchronize());  // the engine's work (a reset still queued is dropped: the fresh block is zero)
   return set_record_strands(e, on != 0);
 } GMX_GUARD_INT("gmx_engine_record_strands")
+
+// The limit on a selection's candidates: a launch argument of the coverage kernels (CoverAcc::max_candidates), nothing to allocate.
+// Only while nothing is recorded: the coverage of one job is that of ONE limit, and a task redone after a full log or run on the
+// twin workspace meets the value of its first pass.
+int gmx_engine_set_max_candidates(gmx_engine *e, uint32_t limit) try {
+  if (!e) {
+    gmx_set_error("null engine");
+    return GMX_EINVAL;
+  }
+  if (e->recorded) {
+    gmx_set_error("gmx_engine_set_max_candidates: coverage has been recorded since the last reset (call gmx_engine_reset first)");
+    return GMX_EINVAL;
+  }
+  e->max_candidates = limit;
+  return GMX_OK;
+} GMX_GUARD_INT("gmx_engine_set_max_candidates")
+
+uint32_t gmx_engine_max_candidates(gmx_engine *e) try {
+  return e ? e->max_candidates : 0u;
+} GMX_GUARD_ZERO("gmx_engine_max_candidates")
 
 // The C ABI of a per-read log, shared by the outcome bytes and the position records.
 static int read_log_record(gmx_engine *e, GmxReadLog gmx_engine::*log, int on) {

@@ -1028,7 +1028,8 @@ struct SearchOut {
                              // (filter kernels, large-capacity passes) [4] exact_mapped (whoever finished the search)
   // Per-read outcomes (gmx_engine_record_outcomes; null: not recorded — one uniform branch per site below). One byte per read,
   // four to a word, read outcome_base + r of the engine's buffer for read r of this launch: bits 0-1 the forward task's code,
-  // 2-3 the reverse-complement task's (GMX_OUTCOME_*), 4 / 5 "its selection drew among several mapping instances". The words
+  // 2-3 the reverse-complement task's (GMX_OUTCOME_*), 4 / 5 "its selection drew among several mapping instances", 6 / 7 "the
+  // limit on candidates left it out: no draw, nothing recorded" (gmx_engine_set_max_candidates; never with 4 / 5). The words
   // start zeroed and every task ORs its code in exactly once, AT THE PLACE THAT COUNTS IT INTO stats[2..4] (a skipped task's
   // code is 0: nothing to write) — so a task redone in a larger tier leaves one code, like one count.
   uint32_t *outcomes;
@@ -1052,8 +1053,10 @@ __device__ __forceinline__ void gmx_outcome_or(const SearchOut &o, uint32_t task
 __device__ __forceinline__ void gmx_outcome_put(const SearchOut &o, uint32_t task, uint32_t code) {
   gmx_outcome_or(o, task, (uint32_t)code << (2u * (task & 1u)));
 }
-__device__ __forceinline__ void gmx_outcome_multi(const SearchOut &o, uint32_t task) {
-  gmx_outcome_or(o, task, GMX_OUTCOME_MULTI << (task & 1u));
+#define GMX_OUTCOME_LEFT_OUT 64u  // (likewise: the limit on candidates left the task out, gmx_engine_set_max_candidates)
+// what a task's selection came to (gmx_cover_task's drawn_from, > 1): it drew among several candidates, or it was left out and did not draw
+__device__ __forceinline__ void gmx_outcome_selection(const SearchOut &o, uint32_t task, uint32_t drawn_from) {
+  gmx_outcome_or(o, task, (drawn_from == GMX_DRAWN_LEFT_OUT ? GMX_OUTCOME_LEFT_OUT : GMX_OUTCOME_MULTI) << (task & 1u));
 }
 // a task's position record: its own eight bytes, one plain 64-bit store (no other task shares them: no atomic)
 __device__ __forceinline__ void gmx_position_put(const SearchOut &o, uint32_t task, uint32_t pos, uint32_t n) {

@@ -633,6 +633,23 @@ int gmx_group_record_strands(gmx_group *g, int on) try {
   return GMX_OK;
 } GMX_GUARD_INT("gmx_group_record_strands")
 
+int gmx_group_set_max_candidates(gmx_group *g, uint32_t limit) try {
+  if (!g || g->ms.empty()) {
+    gmx_set_error("null group");
+    return GMX_EINVAL;
+  }
+  std::vector<uint32_t> before;
+  for (auto &m : g->ms) before.push_back(gmx_engine_max_candidates(m.e));
+  for (size_t i = 0; i < g->ms.size(); ++i) {
+    const int rc = gmx_engine_set_max_candidates(g->ms[i].e, limit);
+    if (rc) {  // all or none: the members before go back to the limit they had
+      for (size_t j = 0; j < i; ++j) (void)gmx_engine_set_max_candidates(g->ms[j].e, before[j]);
+      return rc;
+    }
+  }
+  return GMX_OK;
+} GMX_GUARD_INT("gmx_group_set_max_candidates")
+
 int gmx_comm_unique_id(uint8_t *out128) try {
   if (!rccl().ok) {
     gmx_set_error("RCCL (librccl.so) could not be loaded");

@@ -98,7 +98,14 @@ const char *kGenotypeHelp =
     "                              the grouped allele counts that contain its haplogroup (raw totals) — and SB, the phred-scaled\n"
     "                              two-sided Fisher exact probability of the table (called haplogroups, all others) x (forward,\n"
     "                              reverse); in the VCF they are the last three FORMAT fields, `.:.:.` at a null call. Every other\n"
-    "                              field and file stays as it is; no filter is applied\n";
+    "                              field and file stays as it is; no filter is applied\n"
+    "  --max_candidates arg        leave ambiguous reads out of the coverage (engine extension): N >= 1. A read orientation that\n"
+    "                              maps exactly into a variant site and whose placement would be drawn at random among more\n"
+    "                              than N candidates (its mapping instances outside every site, plus its distinct sets of sites)\n"
+    "                              records no coverage; it still counts as exactly mapped. 1 keeps only reads whose placement\n"
+    "                              needs no draw: the coverage then does not depend on --seed. Writes\n"
+    "                              genotype_dir/read_filter.json: max_candidates, reads, tasks_mapped, tasks_left_out. With\n"
+    "                              --read_outcomes, bits 6 / 7 of a read's byte mark the orientation left out\n";
 
 [[noreturn]] void die(const std::string &msg, int code = 1) {
   std::cout << msg << std::endl;
@@ -1427,6 +1434,15 @@ int run_genotype(const Args &a) {
     else if (m != "gcc11")
       die("--rng_compat must be gcc11 or gcc10");
   }
+  // --max_candidates N: the engines' limit on a selection's candidates (gmx_group_set_max_candidates), N >= 1
+  uint32_t max_candidates = 0;
+  if (a.has("max_candidates")) {
+    const std::string v = a.one("max_candidates");
+    const bool digits = !v.empty() && v.size() <= 10 && v.find_first_not_of("0123456789") == std::string::npos;
+    const unsigned long long n = digits ? std::stoull(v) : 0ull;
+    if (n < 1 || n > 0xFFFFFFFFull) die("--max_candidates takes a whole number >= 1 (got '" + v + "')");
+    max_candidates = (uint32_t)n;
+  }
   for (auto const &smp : samples) {
     mkdirs(join(smp.run_dir, "coverage"));
     mkdirs(join(smp.run_dir, "genotype"));
@@ -1536,7 +1552,9 @@ int run_genotype(const Args &a) {
     std::vector<ReadLogSeg> segs;
   };
   const unsigned char outcome_header[16] = {'G', 'M', 'X', 'O', 1, 0, 0, 0}, position_header[16] = {'G', 'M', 'X', 'P', 1, 0, 0, 0};
-  ReadLog outcome_log{a.has("read_outcomes"), "read outcomes", "bytes", 1, outcome_header, gmx_group_outcome_count, gmx_engine_outcome_count, {}};
+  // (--max_candidates counts the tasks it left out from the outcome bytes: recorded then, written only with --read_outcomes)
+  const bool outcomes_file = a.has("read_outcomes");
+  ReadLog outcome_log{outcomes_file || max_candidates != 0, "read outcomes", "bytes", 1, outcome_header, gmx_group_outcome_count, gmx_engine_outcome_count, {}};
   ReadLog position_log{a.has("read_positions"), "read positions", "records", 16, position_header, gmx_group_position_count, gmx_engine_position_count, {}};
   if (outcome_log.on)
     for (int d = 0; d < gmx_group_size(grp); ++d) GMX_CHECK(gmx_engine_record_outcomes(gmx_group_engine(grp, d), 1));
@@ -1547,6 +1565,7 @@ int run_genotype(const Args &a) {
   // --strand_bias: the same recording; the infer stage reads both strands' grouped counts (gmx_infer_annotate_strands)
   const bool strand_bias = a.has("strand_bias");
   if (strand_coverage || strand_bias) GMX_CHECK(gmx_group_record_strands(grp, 1));
+  if (max_candidates) GMX_CHECK(gmx_group_set_max_candidates(grp, max_candidates));  // before the first reads file; a reset between samples keeps it
   auto note_outcomes = [&](int engine, uint64_t n) {  // BEFORE the call that hands n reads to `engine` (or to the group)
     if (n == 0) return;
     for (ReadLog *log : {&outcome_log, &position_log}) {
@@ -1818,9 +1837,26 @@ int run_genotype(const Args &a) {
 
   // The three coverage files and read_stats.json are written on a thread of their own, beside the genotyping model below
   // (round 5: at configs[1] they were 42 ms of a call whose mapping takes 24; nothing below reads what they write).
-  if (outcome_log.on) {  // G/read_outcomes.bin + .json
-    std::vector<uint8_t> bytes(std::max<uint64_t>(total_reads, 1));
-    gather_read_log(outcome_log, total_reads, gmx_group_fetch_outcomes, gmx_engine_fetch_outcomes, bytes.data(), 1);
+  std::vector<uint8_t> outcome_bytes;
+  if (outcome_log.on) {
+    outcome_bytes.resize(std::max<uint64_t>(total_reads, 1));
+    gather_read_log(outcome_log, total_reads, gmx_group_fetch_outcomes, gmx_engine_fetch_outcomes, outcome_bytes.data(), 1);
+  }
+  if (max_candidates) {  // G/read_filter.json
+    uint64_t mapped = 0, left_out = 0;
+    for (uint64_t i = 0; i < total_reads; ++i) {
+      const uint8_t b = outcome_bytes[i];
+      mapped += ((b & 3u) == GMX_OUTCOME_MAPPED) + (((b >> 2) & 3u) == GMX_OUTCOME_MAPPED);
+      left_out += ((b & GMX_OUTCOME_LEFT_OUT_FORWARD) != 0) + ((b & GMX_OUTCOME_LEFT_OUT_REVERSE) != 0);
+    }
+    const std::string json_path = join(run_dir, "read_filter.json");
+    std::ofstream o(json_path);
+    o << "{\"max_candidates\":" << max_candidates << ",\"reads\":" << total_reads << ",\"tasks_mapped\":" << mapped
+      << ",\"tasks_left_out\":" << left_out << "}\n";
+    close_checked(o, json_path);
+  }
+  if (outcomes_file) {  // G/read_outcomes.bin + .json
+    const std::vector<uint8_t> &bytes = outcome_bytes;
     const std::string json_path = join(run_dir, "read_outcomes.json");
     write_read_log(outcome_log, join(run_dir, "read_outcomes.bin"), total_reads, bytes.data());
     uint64_t by_value[256] = {0}, by_code[4] = {0};

@@ -573,13 +573,28 @@ class Quasimapper:
     def outcomes(self, first: int = 0, n: int = None) -> np.ndarray:
         """The outcome bytes of reads first .. first + n (default: all recorded), in the order the reads were handed over:
         bits 0-1 the forward task's code, 2-3 the reverse-complement task's (0 skipped, 1 missing k-mer, 2 no exact mapping,
-        3 exactly mapped), bit 4 / 5 that task's selection drew among several mapping instances (gmx_engine_fetch_outcomes)."""
+        3 exactly mapped), bit 4 / 5 that task's selection drew among several mapping instances, bit 6 / 7 the limit on candidates
+        left it out (set_max_candidates) (gmx_engine_fetch_outcomes)."""
         return _fetch_read_log(self.lib.gmx_engine_fetch_outcomes, self.h, "outcomes", self.outcome_count(), first, n, (), np.uint8)
 
     def record_strands(self, on: bool = True):
         """Coverage per strand (gmx_engine_record_strands): what the reads as given recorded and what their reverse complements
         recorded are kept apart; see coverage(strand=...). Only while nothing is recorded: after creation or reset()."""
         check(self.lib.gmx_engine_record_strands(self.h, 1 if on else 0))
+
+    def set_max_candidates(self, n: int):
+        """A limit on a selection's candidates (gmx_engine_set_max_candidates; 0: none): a task with a variant-site class whose
+        seeded draw would range over more than ``n`` candidates (instances outside every site + classes) makes no draw and
+        records no coverage; it still counts as exactly mapped, and bit 6 / 7 of its outcome byte marks it. Only while nothing
+        is recorded: after creation or reset()."""
+        if not 0 <= int(n) <= 0xFFFFFFFF:
+            raise ValueError("max_candidates must be in 0 .. 2^32 - 1")
+        check(self.lib.gmx_engine_set_max_candidates(self.h, int(n)))
+
+    @property
+    def max_candidates(self) -> int:
+        """The limit in force (0: none)."""
+        return int(self.lib.gmx_engine_max_candidates(self.h))
 
     def record_positions(self, on: bool = True):
         """From the next mapping call on every read leaves a position record (gmx_engine_record_positions); see positions()."""
@@ -967,6 +982,12 @@ class QuasimapperGroup:
     def record_strands(self, on: bool = True):
         """Coverage per strand on every member (gmx_group_record_strands; Quasimapper.record_strands)."""
         check(self.lib.gmx_group_record_strands(self.h, 1 if on else 0))
+
+    def set_max_candidates(self, n: int):
+        """The limit on candidates on every member, or on none (gmx_group_set_max_candidates; Quasimapper.set_max_candidates)."""
+        if not 0 <= int(n) <= 0xFFFFFFFF:
+            raise ValueError("max_candidates must be in 0 .. 2^32 - 1")
+        check(self.lib.gmx_group_set_max_candidates(self.h, int(n)))
 
     def outcome_count(self) -> int:
         return check(self.lib.gmx_group_outcome_count(self.h))

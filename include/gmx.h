@@ -507,7 +507,9 @@ int gmx_coverage_fetch(gmx_engine *e, uint32_t *allele_sum, uint32_t *per_base, 
 /* Per-read outcomes: what became of every read, one byte each (off by default; nothing changes while it is off).
  *   bits 0-1  the forward task            bits 2-3  the reverse-complement task (0 when the engine maps forward only)
  *   bit 4 / 5 the forward / reverse-complement task's selection drew among more than one mapping instance
- *   bits 6-7  zero
+ *   bit 6 / 7 the forward / reverse-complement task was left out by the limit on candidates (gmx_engine_set_max_candidates):
+ *             exactly mapped (code 3), but it made no draw and recorded no coverage; such a task never has bit 4 / 5. Zero
+ *             while no limit is set.
  * Task codes: 0 skipped (shorter than k, or unencodable), 1 a k-mer of the read is not in the index, 2 no exact mapping,
  * 3 exactly mapped: over all reads the codes add up to the four counters of gmx_stats behind all_reads_count. While recording
  * is on every mapping call, of every feed, appends its reads' bytes to a buffer the engine owns, in the order the reads were
@@ -519,6 +521,8 @@ int gmx_coverage_fetch(gmx_engine *e, uint32_t *allele_sum, uint32_t *per_base, 
 #define GMX_OUTCOME_MAPPED 3
 #define GMX_OUTCOME_MULTI_FORWARD 0x10
 #define GMX_OUTCOME_MULTI_REVERSE 0x20
+#define GMX_OUTCOME_LEFT_OUT_FORWARD 0x40
+#define GMX_OUTCOME_LEFT_OUT_REVERSE 0x80
 int gmx_engine_record_outcomes(gmx_engine *e, int on);
 int64_t gmx_engine_outcome_count(gmx_engine *e);
 int gmx_engine_fetch_outcomes(gmx_engine *e, uint64_t first, uint64_t n, uint8_t *out);
@@ -532,12 +536,29 @@ int gmx_engine_fetch_outcomes(gmx_engine *e, uint64_t first, uint64_t n, uint8_t
  *   pos  0-based index into the linearised PRG (the integer vector the index was built from: the coordinate of
  *        gmx_index_copy_sa and of the rows of gmx_index_copy_pos_info) of the first base of the oriented read — the SMALLEST
  *        such position among the instances the selection chose from: all of them when the task has no variant-site class,
+ *        or was left out by the limit on candidates (nothing drawn: gmx_engine_set_max_candidates),
  *        the instances outside every site when the seeded draw fell on them, else the instances of the drawn class. The
  *        minimum makes the record independent of the order in which the engine's tiers find the states.
  * Buffer, order, resets and the fetch are those of the outcome bytes above; the two recordings are independent. */
 int gmx_engine_record_positions(gmx_engine *e, int on);
 int64_t gmx_engine_position_count(gmx_engine *e);
 int gmx_engine_fetch_positions(gmx_engine *e, uint64_t first, uint64_t n, uint32_t *out);
+/* A limit on a selection's candidates (an engine extension; 0 = none, the default: nothing changes while it is 0). A read that
+ * maps exactly to several places is assigned by a seeded draw among its candidates: the mapping instances outside every site, one
+ * candidate each, and the task's classes (distinct sets of level-0 sites), one each — the reference's random_select_entry. With
+ * the limit set to L >= 1 a task that has at least one class and more than L candidates is LEFT OUT: it makes no draw and
+ * records no coverage (no allele-sum, no grouped count, dense or logged, no per-base count), as MAPQ-0 filtering does elsewhere.
+ * It is still an exactly mapped task: the five read counters are what they are without the limit, its outcome code stays 3 (bit
+ * 6 / 7 of the outcome byte marks it), and its position record keeps n, with pos the smallest position among ALL its instances.
+ * A task without a class records nothing anyway and is not "left out". L = 1 keeps only reads whose placement needs no draw:
+ * the coverage then no longer depends on the seeds or on gmx_engine_opts::rng_mode. The criterion is the draw's range, not the
+ * position record's n (which counts two states at one text position on different allele paths of a nested site as two).
+ *   gmx_engine_set_max_candidates  may only be called while nothing is recorded (the rule of gmx_engine_record_strands below;
+ *     GMX_EINVAL otherwise): one job's coverage is that of one limit. gmx_group_set_max_candidates sets all members of a group,
+ *     or none; under gmx_comm_* every rank sets the same value before it maps (nothing can check that across processes).
+ *   gmx_engine_max_candidates      the limit in force. */
+int gmx_engine_set_max_candidates(gmx_engine *e, uint32_t limit);
+uint32_t gmx_engine_max_candidates(gmx_engine *e);
 /* Coverage per strand (off by default; nothing changes while it is off). Every read is mapped as given and reverse-complemented;
  * with recording on, the engine keeps TWO accumulator blocks — what the reads as given added, and what their reverse complements
  * added — instead of one: allele-sum, dense grouped counts and per-base counts of every site, each per strand. The read counters
@@ -695,6 +716,9 @@ int gmx_group_fetch_positions(gmx_group *g, uint64_t first, uint64_t n, uint32_t
  * members or none: when one cannot be switched, those before it go back. After gmx_group_allreduce every member's two blocks
  * hold the whole job's per-strand totals. */
 int gmx_group_record_strands(gmx_group *g, int on);
+/* The limit on candidates on every member (gmx_engine_set_max_candidates; the same rule). All members or none: when one refuses,
+ * those before it go back to the limit they had. */
+int gmx_group_set_max_candidates(gmx_group *g, uint32_t limit);
 
 typedef struct gmx_comm gmx_comm; /* one engine per PROCESS (torch.distributed.run, mpirun, ...): rank 0 makes the id,
                                      the launcher's own channel broadcasts its 128 bytes, every rank creates its comm */
