@@ -676,16 +676,21 @@ struct Genotyper {
       std::default_random_engine rng(42);  // GCP::Model's generator
       std::vector<double> sim;
       for (size_t i = at; i < N; ++i) {  // ModelDataProducer::produce_data, runner.cpp:254-293
+        // The reference draws these as CovCount (uint16). A draw whose Poisson mean lies above 65535 — a negative binomial of
+        // mean 41 000 and wide variance makes one within a few draws — is then rejected for ever: a site deeper than 65 535
+        // reads would hang the stage. Drawn as uint32 the engine's stream and every value up to 65535 are the same (the range
+        // test is the only difference), and what lies above saturates like a per-base counter.
+        auto to_cov = [](uint32_t v) { return (CovCount)std::min<uint32_t>(v, 65535u); };
         CovCount correct;
         if (!ls.pmf_full.negbinom) {
-          std::poisson_distribution<CovCount> d(ls.mean_cov);
-          correct = d(rng);
+          std::poisson_distribution<uint32_t> d(ls.mean_cov);
+          correct = to_cov(d(rng));
         } else {
-          std::negative_binomial_distribution<CovCount> d(ls.num_successes, ls.success_prob);
-          correct = d(rng);
+          std::negative_binomial_distribution<uint32_t> d(ls.num_successes, ls.success_prob);
+          correct = to_cov(d(rng));
         }
-        std::binomial_distribution<CovCount> b(ls.mean_cov, ls.mean_pb_error);
-        const CovCount incorrect = b(rng);
+        std::binomial_distribution<uint32_t> b((uint32_t)std::min(ls.mean_cov, 4294967295.), ls.mean_pb_error);
+        const CovCount incorrect = to_cov(b(rng));
         Alleles als(2);
         als[0].seq = "C";
         als[0].pb = {correct};

@@ -99,6 +99,13 @@ def fused_coverage_tensor(qm):
     return torch.as_tensor(_DevArray(dc.fused, dc.n_fused, "<i4"), device="cuda")
 
 
+def stats_tensor(qm):
+    """One int64 tensor aliasing the engine's five uint64 read counters (gmx_device_coverage.stats), bit for bit."""
+    import torch
+    dc = qm.device_coverage()
+    return torch.as_tensor(_DevArray(dc.stats, dc.n_stats, "<i8"), device="cuda")
+
+
 def allreduce_device_coverage(qm, dist, tensor=None, stream=None):
     """The exchange through torch.distributed (RCCL): one all-reduce(sum), in place on the engine's coverage block
     (uint32 totals wrap exactly like int32 sums; the uint64 read counters travel as 16-bit limbs), and — when the PRG

@@ -1,7 +1,12 @@
 """uint16 semantics under real depth: more than 65 536 reads over one small site. The reference's
 counters are uint16: allele-sum and grouped counts wrap (data_types.hpp:52), per-base saturates at 65535
 (allele_base.cpp:239). The engine accumulates uint32 on the device and applies both as functions of the total, so
-it must equal the oracle (which counts in uint16 like the reference) — also when the reads arrive in two calls."""
+it must equal the oracle (which counts in uint16 like the reference) — also when the reads arrive in two calls.
+
+This file is one engine and one two-allele site with dense counters (the hit-counter path). Totals that pass 65 535 only when
+they are ADDED — by an exchange between engines or ranks, by the two strands' blocks, by the grouped log's counted records — and
+the read counters' 16-bit limbs up to 2^64 are in test_depth_exchange.py (GPU) and test_depth_exchange_host.py (no GPU), on the
+case of depth_common.py."""
 import numpy as np
 import pytest
 
