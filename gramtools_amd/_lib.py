@@ -165,6 +165,9 @@ SYMBOLS = {
     "gmx_engine_position_count": (_i64, [_vp]),
     "gmx_engine_fetch_positions": (C.c_int, [_vp, _u64, _u64, _u32p]),
     "gmx_engine_record_strands": (C.c_int, [_vp, C.c_int]),
+    "gmx_engine_record_site_ambiguity": (C.c_int, [_vp, C.c_int]),
+    "gmx_engine_site_ambiguity": (C.c_int, [_vp]),
+    "gmx_coverage_fetch_site_ambiguity": (C.c_int, [_vp, _u32p, _u32p, _u64]),
     "gmx_engine_set_max_candidates": (C.c_int, [_vp, C.c_uint32]),
     "gmx_engine_max_candidates": (C.c_uint32, [_vp]),
     "gmx_coverage_fetch_strand": (C.c_int, [_vp, C.c_int, _u32p, _u32p, _u32p]),
@@ -181,6 +184,7 @@ SYMBOLS = {
     "gmx_infer_debug_text": (_i64, [_vp, C.c_char_p, _u64]),
     "gmx_infer_site_json": (_i64, [_vp, _u32, C.c_char_p, _u64]),
     "gmx_infer_annotate_strands": (C.c_int, [_vp, _u32p, _u32p, _u32p, _u64, _u32p, _u64]),
+    "gmx_infer_annotate_ambiguity": (C.c_int, [_vp, _u32p, _u32p, _u64]),
     "gmx_strand_bias_phred": (C.c_double, [_u64, _u64, _u64, _u64]),
     "gmx_infer_model": (_i64, [_u32, C.POINTER(C.c_char_p), _u32p, _u32p, _i32p, _u8p, _u32, _u32p, _i32p, _u32p, C.c_int,
                                C.c_double, C.c_double, C.c_double, C.c_char_p, _u64]),
@@ -205,6 +209,7 @@ SYMBOLS = {
     "gmx_group_position_count": (_i64, [_vp]),
     "gmx_group_fetch_positions": (C.c_int, [_vp, _u64, _u64, _u32p]),
     "gmx_group_record_strands": (C.c_int, [_vp, C.c_int]),
+    "gmx_group_record_site_ambiguity": (C.c_int, [_vp, C.c_int]),
     "gmx_group_set_max_candidates": (C.c_int, [_vp, C.c_uint32]),
     "gmx_comm_unique_id": (C.c_int, [_u8p]),
     "gmx_comm_create": (C.c_int, [_u8p, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),

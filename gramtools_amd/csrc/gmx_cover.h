@@ -1050,10 +1050,31 @@ GMX_HD bool gmx_class_add_item(const GmxIndexView &ix, Env &env, uint32_t it, ui
   return gmx_item_per_base(ix, env, it, read_len, n_hull);
 }
 
+// Per-site ambiguity counts (gmx_engine_record_site_ambiguity): two words per site of the engine's site index,
+// [2 s] drawn — ambiguous tasks whose drawn class recorded at site s — and [2 s + 1] passed — candidate placements at s of
+// ambiguous tasks that ended mapped without recording a class. `several`: this task's selection had more than one candidate
+// (set by gmx_cover_task; the cooperative kernel fills it from its own draw). counts == nullptr: off.
+struct GmxTally {
+  uint32_t *counts;
+  bool several;
+  GMX_HD void add(uint32_t site_index, uint32_t which) const {
+#if defined(__HIP_DEVICE_COMPILE__)
+    atomicAdd(&counts[2u * site_index + which], 1u);
+#else
+    counts[2u * site_index + which] += 1u;
+#endif
+  }
+};
+#define GMX_TALLY_DRAWN 0u
+#define GMX_TALLY_PASSED 1u
+
 // The chosen class's loci and hull recorded (allele_base.cpp:230-244, allele_sum.cpp:31-43, grouped_allele_counts.cpp:17-49).
+// tally (optional): with tally->several, +1 on `drawn` of every site the class records at — where the task adds its one grouped
+// count of that site, behind the log's reservation and every check: a task that is turned away and redone has not counted.
 template <class Env>
-GMX_HD void gmx_class_record(const GmxIndexView &ix, Env &env, uint32_t n_loci, uint32_t n_hull) {
+GMX_HD void gmx_class_record(const GmxIndexView &ix, Env &env, uint32_t n_loci, uint32_t n_hull, const GmxTally *tally = nullptr) {
   typedef GmxScratch<Env> S;
+  const bool tally_drawn = tally != nullptr && tally->counts != nullptr && tally->several;
   // --- every capacity check lies behind us except the grouped log: reserve all of this task's words at once ---
   if (env.has_log_sites()) {
     uint32_t words = 0;
@@ -1101,6 +1122,7 @@ GMX_HD void gmx_class_record(const GmxIndexView &ix, Env &env, uint32_t n_loci, 
     bool first_of_site = true;
     for (uint32_t j = 0; j < i && first_of_site; ++j) first_of_site = env.sget(S::loci(env) + 2 * j) != site;
     if (!first_of_site) continue;
+    if (tally_drawn) tally->add((site - 5) >> 1, GMX_TALLY_DRAWN);
     const GmxSite &s = ix.sites[(site - 5) >> 1];
     if (s.grouped_off != GMX_GROUPED_LOG) {
       uint32_t mask = 0;
@@ -1192,13 +1214,30 @@ struct GmxWhere {
 // value is also "> 1"; a real range cannot reach it: it is bounded by the instances a scratch holds)
 #define GMX_DRAWN_LEFT_OUT 0x80000000u
 
+// `passed` of an ambiguous task that is final and records no class: every class adds +1 on every site of its key (the sorted
+// level-0 site set of gmx_item_key; the classes are the runs of equal keys among the sorted items, one walk of the first item's
+// key per run). The unit is candidate placements: a site in the keys of two classes gets 2.
+template <class Env>
+GMX_HD void gmx_tally_passed(Env &env, const GmxTally &tally, uint32_t n_items) {
+  typedef GmxScratch<Env> S;
+  const uint32_t ord = S::order(env);
+  for (uint32_t i = 0; i < n_items; ++i) {
+    const uint32_t it = env.sget(ord + i);
+    if (i > 0 && gmx_key_cmp(env, env.sget(ord + i - 1), it) == 0) continue;
+    const uint32_t kb = S::keys(env) + it * (1 + env.b_max()), len = env.sget(kb);
+    for (uint32_t t = 0; t < len; ++t) tally.add((env.sget(kb + 1 + t) - 5) >> 1, GMX_TALLY_PASSED);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // The whole recording step for one mapped task.
 // ---------------------------------------------------------------------------
 template <class Env>
 GMX_HD void gmx_cover_task(const GmxIndexView &ix, Env &env, const GmxFinalState *finals, uint32_t n_final,
                            uint32_t read_len, uint32_t seed, int rng_mode, uint32_t *drawn_from = nullptr, GmxWhere *where = nullptr,
-                           uint32_t limit = 0) {
+                           uint32_t limit = 0, GmxTally *tally = nullptr) {
+  // tally (optional; counts == nullptr: off): the per-site ambiguity counts (GmxTally). `passed` is added at the two returns
+  //   below where an ambiguous task is final and records nothing, `drawn` by gmx_class_record: never by a task that fails
   // drawn_from (optional): how many mapping instances the selection drew from (0: it did not draw), or GMX_DRAWN_LEFT_OUT: the
   //   selection had more candidates than `limit` and the task was left out
   // limit (0: none; gmx_engine_set_max_candidates): a task whose selection has a class and more than `limit`
@@ -1308,6 +1347,7 @@ GMX_HD void gmx_cover_task(const GmxIndexView &ix, Env &env, const GmxFinalState
       }
       where->pos = m;
     }
+    if (tally && tally->counts) gmx_tally_passed(env, *tally, n_items);  // (total > limit >= 1: ambiguous)
     return;
   }
   uint32_t r;
@@ -1317,7 +1357,11 @@ GMX_HD void gmx_cover_task(const GmxIndexView &ix, Env &env, const GmxFinalState
   }
   if (drawn_from) *drawn_from = total;
   GMX_COVER_PROF(env, 2);
-  if (r <= nonvariant) return;
+  if (r <= nonvariant) {  // the draw fell on the non-variant instances (nonvariant >= 1 and a class: ambiguous)
+    if (tally && tally->counts) gmx_tally_passed(env, *tally, n_items);
+    return;
+  }
+  if (tally) tally->several = total > 1;
   const uint32_t want = r - nonvariant - 1;  // 0-based index in the ordered map
   uint32_t run_begin = 0, run_end = n_items;  // the want-th run of equal keys
   {
@@ -1350,5 +1394,5 @@ GMX_HD void gmx_cover_task(const GmxIndexView &ix, Env &env, const GmxFinalState
   for (uint32_t ri = run_begin; ri < run_end; ++ri)
     if (!gmx_class_add_item(ix, env, env.sget(ord + ri), read_len, n_loci, n_hull)) return;
   GMX_COVER_PROF(env, 3);
-  gmx_class_record(ix, env, n_loci, n_hull);
+  gmx_class_record(ix, env, n_loci, n_hull, tally);
 }

@@ -21,6 +21,11 @@ struct CoverAcc {
   uint32_t n_tasks;
   unsigned long long *stats;   // QuasimapReadsStats counters
   uint32_t rev_off;            // words from `acc` to the reverse-complement tasks' block (gmx_engine_record_strands); 0: one block
+  // Per-site ambiguity counts, two words per site (gmx_engine_record_site_ambiguity, GmxTally): words from `acc` to them, 0: off
+  // — tally() is the pointer, null when off. (An offset in the struct's last four bytes of padding: with a pointer member the
+  // struct grows, and the last-tier instance keeps a copy of it in scratch memory: profiles/site_ambiguity/README.md.)
+  uint32_t tally_off;
+  __device__ __forceinline__ uint32_t *tally() const { return tally_off ? acc + tally_off : nullptr; }
   // the block a task records into, as its offset in words (a task's orientation is task & 1): `acc` stays wave-uniform, the
   // offset is 32 bits per lane (profiles/strand_coverage/README.md: what the kernels' registers make of other forms)
   __device__ __forceinline__ uint32_t off_of(uint32_t task) const { return (task & 1u) ? rev_off : 0u; }
@@ -330,7 +335,8 @@ __device__ uint32_t gmx_tail_item(const GmxIndexView &ix, const BatchView &b, co
   env.log_at = 0;
   uint32_t drawn_from = 0;
   GmxWhere where{0u, 0u, o.positions != nullptr};
-  gmx_cover_task(ix, env, finals, nf, len, b.seeds[task >> 1], acc.rng_mode, &drawn_from, &where, acc.max_candidates);
+  GmxTally tally{acc.tally(), false};
+  gmx_cover_task(ix, env, finals, nf, len, b.seeds[task >> 1], acc.rng_mode, &drawn_from, &where, acc.max_candidates, &tally);
   env.log_abandon();
   if (o.positions && env.status == GMX_TASK_MAPPED) gmx_position_put(o, task, where.pos, where.n);
   if (env.status == GMX_TASK_MAPPED && is_search) {
@@ -463,7 +469,8 @@ __global__ void __launch_bounds__(GMX_BLOCK) gmx_cover_kernel(GmxIndexView ix, B
 #endif
     uint32_t drawn_from = 0;
     GmxWhere where{0u, 0u, o.positions != nullptr};
-    gmx_cover_task(ix, env, finals, nf, len, b.seeds[read], acc.rng_mode, &drawn_from, &where, acc.max_candidates);
+    GmxTally tally{acc.tally(), false};
+    gmx_cover_task(ix, env, finals, nf, len, b.seeds[read], acc.rng_mode, &drawn_from, &where, acc.max_candidates, &tally);
     env.log_abandon();
     if (o.positions && env.status == GMX_TASK_MAPPED) gmx_position_put(o, task, where.pos, where.n);
     if (o.outcomes && env.status == GMX_TASK_MAPPED && drawn_from > 1u) gmx_outcome_selection(o, task, drawn_from);
@@ -608,6 +615,14 @@ __device__ __noinline__ void gmx_coop_position(const uint32_t *sa, uint2 *positi
     mn = min(mn, (uint32_t)__shfl_xor(mn, d, 16));
   }
   if (writer) positions[(base << 1) + task] = make_uint2(mn, n);
+}
+
+// `passed` of a cooperative task that is final and records no class (GmxTally): the first lane of each class walks
+// its key — key word t of lane L is gmx_lds[(kofs + t) * 64 + L] — and adds +1 per site. Out of line, as gmx_coop_position is.
+__device__ __noinline__ void gmx_coop_passed(uint32_t *tally, uint32_t kofs, uint32_t lane, bool walks) {
+  if (!walks) return;
+  const uint32_t len = gmx_lds[kofs * 64u + lane];
+  for (uint32_t t = 0; t < len; ++t) atomicAdd(&tally[2u * ((gmx_lds[(kofs + 1u + t) * 64u + lane] - 5u) >> 1) + GMX_TALLY_PASSED], 1u);
 }
 
 // (amdgpu_waves_per_eu(4, 8): the kernel's four waves per SIMD, 128 registers, stated to the register allocator. Without it the
@@ -791,6 +806,10 @@ gmx_cover_coop_kernel(GmxIndexView ix, BatchView b, SearchOut o, BigOut g, Cover
     if (o.positions)  // (wave-uniform: every lane takes part in the shuffles)
       gmx_coop_position(ix.sa, o.positions, o.position_base, ts.task, members16 != 0u ? member : nonvar, ie.sget(SI::items + 0),
                         ie.sget(SI::items + 1), ie.sget(SI::hull(ie)), have && gl == 0 && !rejected && !failed && err == 0u);
+    // --- per-site ambiguity: a task that is final here and records no class (left out, or the draw fell on the non-variant
+    // instances: more than one candidate either way) is passed over; nothing below can turn it away, so it counts once ---
+    if (acc.tally_off)
+      gmx_coop_passed(acc.tally(), kofs, lane, leader && err == 0u && items16 != 0u && (drawn_from == GMX_DRAWN_LEFT_OUT || (drawn_from != 0u && members16 == 0u)));
     GMX_COOP_PHASE(2);
     // --- the drawn class: its first lane merges the members and records ---
     bool class_overflow = false, class_logfull = false;
@@ -841,7 +860,10 @@ gmx_cover_coop_kernel(GmxIndexView ix, BatchView b, SearchOut o, BigOut g, Cover
         ok = ok && gmx_item_per_base(ix, ce, 0, len, n_hull);
       }
       ce.arena = ts.arena;
-      if (ok) gmx_class_record(ix, ce, n_loci, n_hull);
+      if (ok) {
+        const GmxTally tally{acc.tally(), drawn_from > 1u};
+        gmx_class_record(ix, ce, n_loci, n_hull, &tally);
+      }
       class_overflow = ce.status == GMX_TASK_OVERFLOW;
       class_logfull = ce.status == GMX_TASK_LOGFULL;
       if (ce.status != GMX_TASK_MAPPED && !class_overflow && !class_logfull) err = ce.status;

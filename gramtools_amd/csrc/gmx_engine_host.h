@@ -80,6 +80,15 @@ struct gmx_engine {
   // Coverage per strand (gmx_engine_record_strands): two accumulator blocks of n_acc words, forward tasks' then reverse-complement
   // tasks' (CoverAcc::rev_off = n_acc), the limbs behind both: n_fused = 2 * n_acc + 32. Off: one block, rev_off = 0.
   bool record_strands = false;
+  // Per-site ambiguity counts (gmx_engine_record_site_ambiguity): 2 * n_sites words (drawn, passed per site) rounded
+  // up to 64, inside the fused block between the accumulator block or blocks and the limbs — the resets, the all-reduce and the
+  // peer-copy fallback carry them as they carry the second block. Off: n_tally = 0. The twin reads its owner's switch.
+  bool record_site_ambiguity = false;
+  size_t n_tally = 0;
+  size_t tally_off() const {  // words from d_fused to them; 0: off
+    const gmx_engine *w = owner ? owner : this;
+    return w->record_site_ambiguity ? (w->record_strands ? 2 : 1) * n_acc : 0;
+  }
   // The limit on a selection's candidates (gmx_engine_set_max_candidates; 0: none). Like record_strands it changes
   // only while nothing is recorded, and the twin reads its owner's: a replay or the second workspace meets the first pass's value.
   uint32_t max_candidates = 0;
@@ -518,6 +527,7 @@ static void gmx_dev_index_release(GmxDeviceIndex *d) {
 
 static int engine_create(const gmx_index *ixh, const gmx_engine_opts *opts_in, gmx_engine *primary, gmx_engine **out);
 static int set_record_strands(gmx_engine *e, bool on);
+static int set_record_site_ambiguity(gmx_engine *e, bool on);
 int gmx_engine_create(const gmx_index *ixh, const gmx_engine_opts *opts_in, gmx_engine **out) try {
   int rc = engine_create(ixh, opts_in, nullptr, out);
   if (rc) return rc;
@@ -542,6 +552,13 @@ int gmx_engine_create(const gmx_index *ixh, const gmx_engine_opts *opts_in, gmx_
   // MEASUREMENT HOOK ONLY (profiles/strand_coverage: the cost of two blocks in an unchanged benchmark): nothing reads them apart
   if (const char *rs = getenv("GMX_RECORD_STRANDS"))
     if (atoi(rs) != 0 && (rc = set_record_strands(e, true))) {
+      gmx_engine_destroy(e);
+      *out = nullptr;
+      return rc;
+    }
+  // MEASUREMENT HOOK ONLY (profiles/site_ambiguity: the cost of the per-site counts in an unchanged benchmark): nothing reads them
+  if (const char *sa = getenv("GMX_RECORD_SITE_AMBIGUITY"))
+    if (atoi(sa) != 0 && (rc = set_record_site_ambiguity(e, true))) {
       gmx_engine_destroy(e);
       *out = nullptr;
       return rc;
@@ -1223,7 +1240,7 @@ static int launch_batch(gmx_engine *e, const BatchInput &in, hipStream_t stream)
   HIP_TRY(hipStreamWaitEvent(e->side_stream, e->ev_fork, 0));
   CoverAcc acc{e->d_fused, e->d_log, e->d_log_cursor, e->log_cap, e->d_scratch_big, e->cover_big_lanes, e->opts.rng_mode,
                (e->owner ? e->owner : e)->max_candidates, e->log_sites ? 1u : 0u, e->d_heap, e->heap_words, e->d_status, (uint32_t)n_reads * 2u, e->d_stats,
-               (e->owner ? e->owner : e)->record_strands ? (uint32_t)e->n_acc : 0u};
+               (e->owner ? e->owner : e)->record_strands ? (uint32_t)e->n_acc : 0u, (uint32_t)e->tally_off()};
   if (seeded) {  // what gmx_seed_kernel sent to the large-capacity pass (reads in repeats), and its coverage: on side 2
     HIP_TRY(hipStreamWaitEvent(e->side2_stream, e->ev_fork, 0));
     const InstPools pools{0};
@@ -2188,18 +2205,23 @@ int gmx_coverage_fetch_strand(gmx_engine *e, int strand, uint32_t *allele_sum, u
 
 // The engine's one-block or two-block allocation. Nothing is recorded and nothing is in flight when this runs, so the new
 // block is simply a zeroed one; the old one stays untouched until the new one exists.
-static int set_record_strands(gmx_engine *e, bool on) {
-  if (e->record_strands == on) return GMX_OK;
-  const size_t n_fused = (on ? 2 : 1) * e->n_acc + 32;
+// Layout of the fused block: [block] or [forward block | reverse block], then [tally: 2 * n_sites words rounded up to 64] when the
+// per-site ambiguity counts are on, then the 32 limb words; 16 words of read counters and the log cursor behind it.
+static int set_block_layout(gmx_engine *e, bool strands, bool site_ambiguity, const char *who) {
+  if (e->record_strands == strands && e->record_site_ambiguity == site_ambiguity) return GMX_OK;
+  const size_t n_tally = site_ambiguity ? (2 * (size_t)e->dview.n_sites + 63) / 64 * 64 : 0;
+  const size_t n_fused = (strands ? 2 : 1) * e->n_acc + n_tally + 32;
   if (n_fused + 32 > 0xFFFFFFFFull) {  // (the resets' word counts and CoverAcc::rev_off are 32 bits)
-    gmx_set_error("gmx_engine_record_strands: two accumulator blocks of this index exceed 2^32 words");
+    gmx_set_error(std::string(who) + ": the accumulator blocks of this index exceed 2^32 words");
     return GMX_EINVAL;
   }
   uint32_t *old = e->d_fused, *q = nullptr;
   int rc = e->alloc(&q, n_fused + 32, true);  // + 16 words of read counters + log cursor
   if (rc) return rc;
   e->release(old);
-  e->record_strands = on;
+  e->record_strands = strands;
+  e->record_site_ambiguity = site_ambiguity;
+  e->n_tally = n_tally;
   e->reset_pending = false;  // (a queued reset: the fresh block is zero)
   for (gmx_engine *w : {e, e->twin}) {  // the twin's alias of the block and every derived pointer follow
     if (!w) continue;
@@ -2211,20 +2233,63 @@ static int set_record_strands(gmx_engine *e, bool on) {
   }
   return GMX_OK;
 }
+static int set_record_strands(gmx_engine *e, bool on) { return set_block_layout(e, on, e->record_site_ambiguity, "gmx_engine_record_strands"); }
+static int set_record_site_ambiguity(gmx_engine *e, bool on) {
+  return set_block_layout(e, e->record_strands, on, "gmx_engine_record_site_ambiguity");
+}
 
-int gmx_engine_record_strands(gmx_engine *e, int on) try {
+// The C ABI of a switch of the block's layout: only while nothing is recorded
+static int block_layout_switch(gmx_engine *e, int (*set)(gmx_engine *, bool), int on, const char *who) {
   if (!e) {
     gmx_set_error("null engine");
     return GMX_EINVAL;
   }
   if (e->recorded) {
-    gmx_set_error("gmx_engine_record_strands: coverage has been recorded since the last reset (call gmx_engine_reset first)");
+    gmx_set_error(std::string(who) + ": coverage has been recorded since the last reset (call gmx_engine_reset first)");
     return GMX_EINVAL;
   }
   HIP_TRY(hipSetDevice(e->opts.device));
   HIP_TRY(hipDeviceSynchronize());  // the engine's work (a reset still queued is dropped: the fresh block is zero)
-  return set_record_strands(e, on != 0);
+  return set(e, on != 0);
+}
+
+int gmx_engine_record_strands(gmx_engine *e, int on) try {
+  return block_layout_switch(e, set_record_strands, on, "gmx_engine_record_strands");
 } GMX_GUARD_INT("gmx_engine_record_strands")
+
+int gmx_engine_record_site_ambiguity(gmx_engine *e, int on) try {
+  return block_layout_switch(e, set_record_site_ambiguity, on, "gmx_engine_record_site_ambiguity");
+} GMX_GUARD_INT("gmx_engine_record_site_ambiguity")
+
+int gmx_engine_site_ambiguity(gmx_engine *e) try {
+  return e && e->record_site_ambiguity ? 1 : 0;
+} GMX_GUARD_ZERO("gmx_engine_site_ambiguity")
+
+int gmx_coverage_fetch_site_ambiguity(gmx_engine *e, uint32_t *drawn, uint32_t *passed, uint64_t n_sites) try {
+  if (!e || (n_sites && (!drawn || !passed))) {
+    gmx_set_error("gmx_coverage_fetch_site_ambiguity: null argument");
+    return GMX_EINVAL;
+  }
+  if (!e->record_site_ambiguity) {
+    gmx_set_error("gmx_coverage_fetch_site_ambiguity: the engine does not record them (gmx_engine_record_site_ambiguity)");
+    return GMX_EINVAL;
+  }
+  if (n_sites != e->dview.n_sites) {
+    gmx_set_error("gmx_coverage_fetch_site_ambiguity: n_sites is " + std::to_string(n_sites) + ", the index has " + std::to_string(e->dview.n_sites));
+    return GMX_EINVAL;
+  }
+  {  // (a task redone after a full log counts then; both workspaces' streams)
+    int rc = fetch_blocks(e, 0, 0, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+  }
+  std::vector<uint32_t> w(std::max<size_t>(2 * (size_t)n_sites, 1));
+  if (n_sites) HIP_TRY(hipMemcpy(w.data(), e->d_fused + e->tally_off(), 2 * (size_t)n_sites * 4, hipMemcpyDeviceToHost));
+  for (size_t s = 0; s < n_sites; ++s) {
+    drawn[s] = w[2 * s];
+    passed[s] = w[2 * s + 1];
+  }
+  return GMX_OK;
+} GMX_GUARD_INT("gmx_coverage_fetch_site_ambiguity")
 
 // The limit on a selection's candidates: a launch argument of the coverage kernels (CoverAcc::max_candidates), nothing to allocate.
 // Only while nothing is recorded: the coverage of one job is that of ONE limit, and a task redone after a full log or run on the
@@ -2399,6 +2464,7 @@ void gmx_engine_raw(gmx_engine *e, GmxEngineRaw *out) {
   out->n_fused = e->n_fused;
   out->log_sites = e->log_sites;
   out->record_strands = e->record_strands;
+  out->record_site_ambiguity = e->record_site_ambiguity;
 }
 
 int gmx_engine_log_export(gmx_engine *e, std::vector<uint32_t> &out) {

@@ -122,6 +122,9 @@ struct Site {  // GenotypedSite + LevelGenotypedSite (interfaces.hpp:49-132, lev
   // gmx_infer_annotate_strands: per output allele, the grouped counts of the groups with its haplogroup, per strand (raw
   // 64-bit sums), and the strand-bias score of the call; a null site keeps the flag and has no values
   bool has_strands = false;
+  // gmx_infer_annotate_ambiguity: the engine's per-site ambiguity counts of this site (AMB_DRAWN, AMB_PASSED)
+  bool has_ambiguity = false;
+  uint32_t amb_drawn = 0, amb_passed = 0;
   std::vector<uint64_t> cov_fwd, cov_rev;
   double sb = 0.;
   bool is_null() const { return !genotype.empty() && genotype[0] == -1; }
@@ -807,13 +810,22 @@ std::string jdouble(double v) {  // nlohmann::json's float form: shortest round 
 
 const char *kGtConfDesc = "Genotype confidence as likelihood ratio of called and next most likely genotype.";
 const char *kGcpDesc = "Percent of calls expected to have lower GT_CONF";
+const char *kAmbDrawnDesc = "Reads recorded at this site by a seeded draw among several candidate placements";
+const char *kAmbPassedDesc = "Candidate placements (not reads) at this site of reads that recorded no variant-site placement: left out by the limit on candidates, or drawn outside every site";
 const char *kAmbigDesc = "Ambiguous site. Different variant paths can produce the same sequence.";
 
 std::string site_json(const Site &s, const std::string *seg, size_t pos1) {  // make_json_site, make_json.cpp:60-82
   std::ostringstream o;
   o << "{\"ALS\":[";
   for (size_t i = 0; i < s.alleles.size(); ++i) o << (i ? "," : "") << jstr(s.alleles[i].seq);
-  o << "],\"COV\":[[";
+  o << "]";
+  if (s.has_ambiguity) {
+    if (s.is_null())
+      o << ",\"AMB_DRAWN\":[null],\"AMB_PASSED\":[null]";
+    else
+      o << ",\"AMB_DRAWN\":[" << s.amb_drawn << "],\"AMB_PASSED\":[" << s.amb_passed << "]";
+  }
+  o << ",\"COV\":[[";
   for (size_t i = 0; i < s.covs.size(); ++i) o << (i ? "," : "") << jdouble(s.covs[i]);
   o << "]]";
   if (s.has_strands) {
@@ -947,6 +959,7 @@ using LogGroups = std::vector<std::vector<std::pair<AlleleIds, uint64_t>>>;
 struct gmx_infer {
   const gmx_index *ix = nullptr;
   std::unique_ptr<Genotyper> g;
+  bool ambiguity = false;  // gmx_infer_annotate_ambiguity has run: the writers add AMB_DRAWN and AMB_PASSED
   bool strands = false;  // gmx_infer_annotate_strands has run: the writers add COV_FWD, COV_REV and SB
 };
 
@@ -1171,6 +1184,21 @@ int gmx_infer_annotate_strands(gmx_infer *inf, const uint32_t *grouped_dense_fwd
   inf->strands = true;
   return GMX_OK;
 } GMX_GUARD_INT("gmx_infer_annotate_strands")
+
+int gmx_infer_annotate_ambiguity(gmx_infer *inf, const uint32_t *drawn, const uint32_t *passed, uint64_t n_sites) try {
+  if (!inf || !inf->g || (n_sites && (!drawn || !passed))) return fail("gmx_infer_annotate_ambiguity: null argument");
+  Genotyper &g = *inf->g;
+  if (n_sites != g.recs.size())
+    return fail("gmx_infer_annotate_ambiguity: n_sites is " + std::to_string(n_sites) + ", the index has " + std::to_string(g.recs.size()));
+  for (size_t si = 0; si < g.recs.size(); ++si) {
+    Site &s = *g.recs[si];
+    s.has_ambiguity = true;
+    s.amb_drawn = s.is_null() ? 0u : drawn[si];
+    s.amb_passed = s.is_null() ? 0u : passed[si];
+  }
+  inf->ambiguity = true;
+  return GMX_OK;
+} GMX_GUARD_INT("gmx_infer_annotate_ambiguity")
 
 int64_t gmx_infer_site_json(const gmx_infer *inf, uint32_t site_index, char *out, uint64_t cap) try {
   if (!inf || site_index >= inf->g->recs.size()) return fail("gmx_infer_site_json: bad argument");
@@ -1524,7 +1552,9 @@ int gmx_infer_write_json(const gmx_infer *inf, const char *coords_path, const ch
       }
   }
   o << "],\"Model\":\"LevelGenotyping\",\"Samples\":[{\"Desc\":\"made by gramtools genotype\",\"Name\":" << jstr(sample_id ? sample_id : "")
-    << "}],\"Site_Fields\":{\"ALS\":{\"Desc\":\"Alleles at this site\"},\"COV\":{\"Desc\":\"Read coverage on each allele\"},"
+    << "}],\"Site_Fields\":{\"ALS\":{\"Desc\":\"Alleles at this site\"},"
+    << (inf->ambiguity ? "\"AMB_DRAWN\":{\"Desc\":" + jstr(kAmbDrawnDesc) + "},\"AMB_PASSED\":{\"Desc\":" + jstr(kAmbPassedDesc) + "}," : std::string())
+    << "\"COV\":{\"Desc\":\"Read coverage on each allele\"},"
            << (inf->strands ? "\"COV_FWD\":{\"Desc\":" + jstr(kCovFwdDesc) + "},\"COV_REV\":{\"Desc\":" + jstr(kCovRevDesc) + "}," : std::string())
     << "\"DP\":{\"Desc\":\"Total read depth on variant site\"},\"FT\":{\"Desc\":\"Filters failed in a sample\"},"
        "\"GT\":{\"Desc\":\"Genotype\"},\"GT_CONF\":{\"Desc\":"
@@ -1580,6 +1610,9 @@ int gmx_infer_write_vcf(const gmx_infer *inf, const char *coords_path, const cha
     hd << "##FORMAT=<ID=COV_FWD,Number=R,Type=Integer,Description=\"" << kCovFwdDesc << "\",Source=\"gramtools\">\n"
        << "##FORMAT=<ID=COV_REV,Number=R,Type=Integer,Description=\"" << kCovRevDesc << "\",Source=\"gramtools\">\n"
        << "##FORMAT=<ID=SB,Number=1,Type=Float,Description=\"" << kSbDesc << "\",Source=\"gramtools\">\n";
+  if (inf->ambiguity)
+    hd << "##FORMAT=<ID=AMB_DRAWN,Number=1,Type=Integer,Description=\"" << kAmbDrawnDesc << "\",Source=\"gramtools\">\n"
+       << "##FORMAT=<ID=AMB_PASSED,Number=1,Type=Integer,Description=\"" << kAmbPassedDesc << "\",Source=\"gramtools\">\n";
   hd << "##FILTER=<ID=AMBIG,Description=\"" << kAmbigDesc << "\",Source=\"gramtools\">\n"
      << "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" << (sample_id ? sample_id : "sample") << "\n";
   z.write(hd.str());
@@ -1606,7 +1639,8 @@ int gmx_infer_write_vcf(const gmx_infer *inf, const char *coords_path, const cha
     else
       for (size_t a = 1; a < s.alleles.size(); ++a) r << (a > 1 ? "," : "") << s.alleles[a].seq;
     const bool has_cov = !s.covs.empty();
-    r << "\t.\t.\t.\tGT:DP" << (has_cov ? ":COV" : "") << ":FT:GT_CONF:GT_CONF_PERCENTILE" << (s.has_strands ? ":COV_FWD:COV_REV:SB" : "") << "\t";
+    r << "\t.\t.\t.\tGT:DP" << (has_cov ? ":COV" : "") << ":FT:GT_CONF:GT_CONF_PERCENTILE" << (s.has_strands ? ":COV_FWD:COV_REV:SB" : "")
+      << (s.has_ambiguity ? ":AMB_DRAWN:AMB_PASSED" : "") << "\t";
     if (s.is_null())
       r << ".";
     else
@@ -1632,6 +1666,12 @@ int gmx_infer_write_vcf(const gmx_infer *inf, const char *coords_path, const cha
         for (size_t k = 0; k < s.cov_rev.size(); ++k) r << (k ? "," : "") << s.cov_rev[k];
         r << ":" << fmt_g(s.sb);
       }
+    }
+    if (s.has_ambiguity) {
+      if (s.is_null())
+        r << ":.:.";
+      else
+        r << ":" << s.amb_drawn << ":" << s.amb_passed;
     }
     r << "\n";
     acc += r.str();

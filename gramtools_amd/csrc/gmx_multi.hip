@@ -597,11 +597,14 @@ int gmx_group_allreduce(gmx_group *g) try {
   for (auto &m : g->ms) {
     int rc = gmx_engine_sync(m.e);
     if (rc) return rc;
-    gmx_engine_raw(m.e, &m.raw);  // (gmx_engine_record_strands replaces the block)
+    gmx_engine_raw(m.e, &m.raw);  // (gmx_engine_record_strands and gmx_engine_record_site_ambiguity replace the block)
   }
   for (auto &m : g->ms)
-    if (m.raw.record_strands != g->ms[0].raw.record_strands || m.raw.n_fused != g->ms[0].raw.n_fused) {
-      gmx_set_error("gmx_group_allreduce: the members disagree on per-strand recording (gmx_group_record_strands sets all of them)");
+    if (m.raw.record_strands != g->ms[0].raw.record_strands || m.raw.record_site_ambiguity != g->ms[0].raw.record_site_ambiguity ||
+        m.raw.n_fused != g->ms[0].raw.n_fused) {
+      gmx_set_error(m.raw.record_strands != g->ms[0].raw.record_strands
+                        ? "gmx_group_allreduce: the members disagree on per-strand recording (gmx_group_record_strands sets all of them)"
+                        : "gmx_group_allreduce: the members disagree on the per-site ambiguity counts (gmx_group_record_site_ambiguity sets all of them)");
       return GMX_EINVAL;
     }
   int rc = g->use_rccl ? gmx_exchange(g->ms, (int)g->ms.size()) : gmx_exchange_peer(g->ms);
@@ -613,17 +616,18 @@ int gmx_group_allreduce(gmx_group *g) try {
   return GMX_OK;
 } GMX_GUARD_INT("gmx_group_allreduce")
 
-int gmx_group_record_strands(gmx_group *g, int on) try {
+// A switch of the members' block layout (per-strand blocks, per-site ambiguity counts): all members or none
+static int group_layout_switch(gmx_group *g, int (*set)(gmx_engine *, int), bool GmxEngineRaw::*field, int on) {
   if (!g || g->ms.empty()) {
     gmx_set_error("null group");
     return GMX_EINVAL;
   }
   for (auto &m : g->ms) gmx_engine_raw(m.e, &m.raw);  // (what every member records now)
   for (size_t i = 0; i < g->ms.size(); ++i) {
-    const int rc = gmx_engine_record_strands(g->ms[i].e, on);
+    const int rc = set(g->ms[i].e, on);
     if (rc) {  // all or none: the members before go back to what they recorded
       for (size_t j = 0; j < i; ++j) {
-        (void)gmx_engine_record_strands(g->ms[j].e, g->ms[j].raw.record_strands ? 1 : 0);
+        (void)set(g->ms[j].e, g->ms[j].raw.*field ? 1 : 0);
         gmx_engine_raw(g->ms[j].e, &g->ms[j].raw);
       }
       return rc;
@@ -631,7 +635,15 @@ int gmx_group_record_strands(gmx_group *g, int on) try {
   }
   for (auto &m : g->ms) gmx_engine_raw(m.e, &m.raw);
   return GMX_OK;
+}
+
+int gmx_group_record_strands(gmx_group *g, int on) try {
+  return group_layout_switch(g, gmx_engine_record_strands, &GmxEngineRaw::record_strands, on);
 } GMX_GUARD_INT("gmx_group_record_strands")
+
+int gmx_group_record_site_ambiguity(gmx_group *g, int on) try {
+  return group_layout_switch(g, gmx_engine_record_site_ambiguity, &GmxEngineRaw::record_site_ambiguity, on);
+} GMX_GUARD_INT("gmx_group_record_site_ambiguity")
 
 int gmx_group_set_max_candidates(gmx_group *g, uint32_t limit) try {
   if (!g || g->ms.empty()) {

@@ -105,7 +105,15 @@ const char *kGenotypeHelp =
     "                              records no coverage; it still counts as exactly mapped. 1 keeps only reads whose placement\n"
     "                              needs no draw: the coverage then does not depend on --seed. Writes\n"
     "                              genotype_dir/read_filter.json: max_candidates, reads, tasks_mapped, tasks_left_out. With\n"
-    "                              --read_outcomes, bits 6 / 7 of a read's byte mark the orientation left out\n";
+    "                              --read_outcomes, bits 6 / 7 of a read's byte mark the orientation left out\n"
+    "  --site_ambiguity            per-site ambiguity counts (engine extension): writes coverage/site_ambiguity.json,\n"
+    "                              {\"site_ambiguity\":{\"drawn\":[...],\"passed_over\":[...]}} with one entry per site in the order\n"
+    "                              of allele_sum_coverage — drawn: read orientations recorded at the site by a seeded draw among\n"
+    "                              several candidate placements; passed_over: CANDIDATE PLACEMENTS (not reads) at the site of read\n"
+    "                              orientations that recorded no variant-site placement, left out by --max_candidates or drawn\n"
+    "                              outside every site (outermost sites only) — and genotype_dir/site_ambiguity.json: sites,\n"
+    "                              sites_drawn, sites_passed_over, drawn, passed_over. genotyped.json and genotyped.vcf.gz gain\n"
+    "                              AMB_DRAWN and AMB_PASSED per site (the last two FORMAT fields, `.:.` at a null call)\n";
 
 [[noreturn]] void die(const std::string &msg, int code = 1) {
   std::cout << msg << std::endl;
@@ -1565,6 +1573,9 @@ int run_genotype(const Args &a) {
   // --strand_bias: the same recording; the infer stage reads both strands' grouped counts (gmx_infer_annotate_strands)
   const bool strand_bias = a.has("strand_bias");
   if (strand_coverage || strand_bias) GMX_CHECK(gmx_group_record_strands(grp, 1));
+  // --site_ambiguity: the engines' per-site counts (gmx_group_record_site_ambiguity), across samples (a reset zeroes them, the mode stays)
+  const bool site_ambiguity = a.has("site_ambiguity");
+  if (site_ambiguity) GMX_CHECK(gmx_group_record_site_ambiguity(grp, 1));
   if (max_candidates) GMX_CHECK(gmx_group_set_max_candidates(grp, max_candidates));  // before the first reads file; a reset between samples keeps it
   auto note_outcomes = [&](int engine, uint64_t n) {  // BEFORE the call that hands n reads to `engine` (or to the group)
     if (n == 0) return;
@@ -1825,6 +1836,37 @@ int run_genotype(const Args &a) {
         die(std::string("gram: grouped log per strand: ") + gmx_last_error());
     }
 
+  std::vector<uint32_t> amb_drawn, amb_passed;  // --site_ambiguity: the job's sums (the exchange carried them with the coverage)
+  if (site_ambiguity) {
+    amb_drawn.assign(std::max<uint32_t>(info.n_sites, 1), 0);
+    amb_passed.assign(std::max<uint32_t>(info.n_sites, 1), 0);
+    GMX_CHECK(gmx_coverage_fetch_site_ambiguity(eng, amb_drawn.data(), amb_passed.data(), info.n_sites));
+    {  // coverage/site_ambiguity.json
+      const std::string path = join(cov_dir, "site_ambiguity.json");
+      std::ofstream o(path);
+      o << "{\"site_ambiguity\":{\"drawn\":[";
+      for (uint32_t s = 0; s < info.n_sites; ++s) o << (s ? "," : "") << amb_drawn[s];
+      o << "],\"passed_over\":[";
+      for (uint32_t s = 0; s < info.n_sites; ++s) o << (s ? "," : "") << amb_passed[s];
+      o << "]}}\n";
+      close_checked(o, path);
+    }
+    {  // G/site_ambiguity.json
+      uint64_t sites_drawn = 0, sites_passed = 0, sum_drawn = 0, sum_passed = 0;
+      for (uint32_t s = 0; s < info.n_sites; ++s) {
+        sites_drawn += amb_drawn[s] != 0;
+        sites_passed += amb_passed[s] != 0;
+        sum_drawn += amb_drawn[s];
+        sum_passed += amb_passed[s];
+      }
+      const std::string path = join(run_dir, "site_ambiguity.json");
+      std::ofstream o(path);
+      o << "{\"sites\":" << info.n_sites << ",\"sites_drawn\":" << sites_drawn << ",\"sites_passed_over\":" << sites_passed
+        << ",\"drawn\":" << sum_drawn << ",\"passed_over\":" << sum_passed << "}\n";
+      close_checked(o, path);
+    }
+  }
+
   gmx_depth_stats ds;  // readstats.compute_coverage_depth, quasimap.cpp:48
   GMX_CHECK(gmx_compute_coverage_depth(ix, per_base.data(), grouped.data(), glog.data(), (uint64_t)n_log, &ds));
   rs.mean_cov_depth = ds.mean_cov_depth;
@@ -2029,6 +2071,7 @@ int run_genotype(const Args &a) {
   if (strand_bias)
     GMX_CHECK(gmx_infer_annotate_strands(inf, strand_grouped[0].data(), strand_grouped[1].data(), strand_log[0].data(), strand_log[0].size(),
                                          strand_log[1].data(), strand_log[1].size()));
+  if (site_ambiguity) GMX_CHECK(gmx_infer_annotate_ambiguity(inf, amb_drawn.data(), amb_passed.data(), info.n_sites));
   const std::string coords = join(gram_dir, "prg_coords.tsv");
   if (a.has("debug")) {  // site_gtyping_debug_info.txt (parameters.cpp:98; genotype.cpp:76-82)
     const std::string dbg_path = join(run_dir, "site_gtyping_debug_info.txt");

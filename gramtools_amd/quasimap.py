@@ -582,6 +582,21 @@ class Quasimapper:
         recorded are kept apart; see coverage(strand=...). Only while nothing is recorded: after creation or reset()."""
         check(self.lib.gmx_engine_record_strands(self.h, 1 if on else 0))
 
+    def record_site_ambiguity(self, on: bool = True):
+        """Per-site ambiguity counts (gmx_engine_record_site_ambiguity); see site_ambiguity(). Only while nothing is recorded:
+        after creation or reset(). The recording survives reset()."""
+        check(self.lib.gmx_engine_record_site_ambiguity(self.h, 1 if on else 0))
+
+    def site_ambiguity(self):
+        """``(drawn, passed)``, two uint32 arrays with one entry per site in allele_sum_coverage's order
+        (gmx_coverage_fetch_site_ambiguity). drawn[s]: tasks whose selection had several candidates, drew a class and recorded it
+        at s. passed[s]: candidate placements (not tasks) at level-0 site s of such tasks that ended mapped and recorded no class —
+        left out by the limit on candidates, or the draw fell outside every site."""
+        n = self.index.n_sites
+        drawn, passed = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+        check(self.lib.gmx_coverage_fetch_site_ambiguity(self.h, _p(drawn, C.c_uint32), _p(passed, C.c_uint32), n))
+        return drawn[:n], passed[:n]
+
     def set_max_candidates(self, n: int):
         """A limit on a selection's candidates (gmx_engine_set_max_candidates; 0: none): a task with a variant-site class whose
         seeded draw would range over more than ``n`` candidates (instances outside every site + classes) makes no draw and
@@ -983,6 +998,18 @@ class QuasimapperGroup:
         """Coverage per strand on every member (gmx_group_record_strands; Quasimapper.record_strands)."""
         check(self.lib.gmx_group_record_strands(self.h, 1 if on else 0))
 
+    def record_site_ambiguity(self, on: bool = True):
+        """Per-site ambiguity counts on every member, or on none (gmx_group_record_site_ambiguity; Quasimapper.record_site_ambiguity)."""
+        check(self.lib.gmx_group_record_site_ambiguity(self.h, 1 if on else 0))
+
+    def site_ambiguity(self, member: int = 0):
+        """Quasimapper.site_ambiguity of engine `member` (after :meth:`allreduce`: the sums of the whole job, on every member)."""
+        view = self._member(member)
+        try:
+            return view.site_ambiguity()
+        finally:
+            view.h = None
+
     def set_max_candidates(self, n: int):
         """The limit on candidates on every member, or on none (gmx_group_set_max_candidates; Quasimapper.set_max_candidates)."""
         if not 0 <= int(n) <= 0xFFFFFFFF:
@@ -1070,6 +1097,15 @@ class Genotyped:
         gf, gr, lf, lr = arr(cov_fwd.raw_grouped), arr(cov_rev.raw_grouped), arr(cov_fwd.raw_grouped_log), arr(cov_rev.raw_grouped_log)
         check(self.lib.gmx_infer_annotate_strands(self.h, _p(gf, C.c_uint32), _p(gr, C.c_uint32), _p(lf, C.c_uint32),
                                                   cov_fwd.raw_grouped_log.size, _p(lr, C.c_uint32), cov_rev.raw_grouped_log.size))
+
+    def annotate_ambiguity(self, drawn, passed):
+        """Per-site ambiguity in the calls (gmx_infer_annotate_ambiguity): site() and the written files gain AMB_DRAWN and
+        AMB_PASSED, from ``qm.site_ambiguity()``."""
+        d, p = np.ascontiguousarray(drawn, dtype=np.uint32), np.ascontiguousarray(passed, dtype=np.uint32)
+        if d.shape != p.shape or d.ndim != 1:
+            raise ValueError("drawn and passed are two arrays of one entry per site")
+        pad = lambda x: x if x.size else np.zeros(1, np.uint32)
+        check(self.lib.gmx_infer_annotate_ambiguity(self.h, _p(pad(d), C.c_uint32), _p(pad(p), C.c_uint32), d.size))
 
     def site(self, i: int) -> dict:
         n = check(self.lib.gmx_infer_site_json(self.h, i, None, 0))

@@ -579,6 +579,30 @@ uint32_t gmx_engine_max_candidates(gmx_engine *e);
  *     must agree, and nothing can check that across processes). */
 int gmx_engine_record_strands(gmx_engine *e, int on);
 int gmx_coverage_fetch_strand(gmx_engine *e, int strand, uint32_t *allele_sum, uint32_t *per_base, uint32_t *grouped_dense);
+/* Per-site ambiguity counts (off by default; nothing changes while it is off). A task is AMBIGUOUS when its selection has at least
+ * one class and more than one candidate (non-variant instances + classes > 1): the condition of the multi and left-out bits of
+ * gmx_engine_fetch_outcomes. With recording on the engine keeps two uint32 counters per site, indexed by the engine's site index
+ * (marker - 5) >> 1, the order of allele_sum_coverage's lines:
+ *   drawn[s]   ambiguous tasks that drew a class and recorded it, once per site s the class records at (where the task adds its
+ *              one grouped count of s; nested child sites like any other). Depends on the seeds: it qualifies the coverage at s.
+ *   passed[s]  CANDIDATE PLACEMENTS, not tasks: every ambiguous task that ends mapped and records no class — left out by the limit
+ *              on candidates, or its draw fell on the non-variant instances — adds, for each of its classes, +1 on every level-0
+ *              site of the class's key. A site in the keys of two classes of one task gets 2. Level-0 sites only. With the limit
+ *              at 1 it depends neither on the seeds nor on rng_mode.
+ * A task counts exactly once, whichever tier, replay or workspace finishes it. Strands are not split.
+ *   gmx_engine_record_site_ambiguity  the rule of gmx_engine_record_strands: only while nothing is recorded (GMX_EINVAL otherwise);
+ *     when the allocation fails the old state stays. Combines with gmx_engine_record_strands.
+ *   gmx_engine_site_ambiguity          1 when recording is on.
+ *   gmx_coverage_fetch_site_ambiguity  both arrays (n_sites words each) once everything handed over has been recorded;
+ *     GMX_EINVAL with recording off or an n_sites that is not the index's.
+ *   gmx_coverage_device                with recording on `fused` is [block(s) | 2 * n_sites words rounded up to 64 | 32 limb
+ *     words]: the exchange sums the counts with the coverage, and after gmx_group_allreduce every member holds the job's. Every
+ *     engine of one exchange must be in the same mode: gmx_group_record_site_ambiguity sets all members of a group or none
+ *     (gmx_group_allreduce returns GMX_EINVAL when they disagree); under gmx_comm_* every rank calls
+ *     gmx_engine_record_site_ambiguity with the same value before it maps (nothing can check that across processes). */
+int gmx_engine_record_site_ambiguity(gmx_engine *e, int on);
+int gmx_engine_site_ambiguity(gmx_engine *e);
+int gmx_coverage_fetch_site_ambiguity(gmx_engine *e, uint32_t *drawn, uint32_t *passed, uint64_t n_sites);
 /* Grouped counts of sites with more than 8 alleles (grouped_allele_counts.cpp:17-49 for sites without dense slots).
  * Returns the number of uint32 words of the log (and copies it when it fits cap_words). The log is a sequence of records
  *   [site_index, n_ids, ids...]                                     worth +1, or
@@ -645,6 +669,11 @@ int64_t gmx_infer_site_json(const gmx_infer *inf, uint32_t site_index, char *out
  * lists; VCF: FORMAT ...:COV_FWD:COV_REV:SB at the end, a null site `.:.:.`); without this call they write what they wrote. */
 int gmx_infer_annotate_strands(gmx_infer *inf, const uint32_t *grouped_dense_fwd, const uint32_t *grouped_dense_rev,
                                const uint32_t *log_fwd, uint64_t n_log_fwd, const uint32_t *log_rev, uint64_t n_log_rev);
+/* Per-site ambiguity in the calls (`gram genotype --site_ambiguity`), after gmx_infer_run: the two arrays of
+ * gmx_coverage_fetch_site_ambiguity (n_sites: the index's). Every site whose genotype is not null gets AMB_DRAWN and AMB_PASSED
+ * (jVCF: two keys, a null site [null]; VCF: two FORMAT fields at the end, behind the strand fields when both are on, a null site
+ * `.`). Without this call the writers write what they wrote. */
+int gmx_infer_annotate_ambiguity(gmx_infer *inf, const uint32_t *drawn, const uint32_t *passed, uint64_t n_sites);
 /* -10 log10 of the two-sided Fisher exact probability of the table [[a, b], [c, d]] (the hypergeometric probabilities of all
  * tables with its margins that are at most P(observed) (1 + 1e-7), summed; capped at 1). +0.0 when p = 1 or a margin is zero.
  * Counts above 2^40 are taken as 2^40 (the log-gamma sums lose their digits beyond; within 1e-6 of the exact value for
@@ -716,6 +745,9 @@ int gmx_group_fetch_positions(gmx_group *g, uint64_t first, uint64_t n, uint32_t
  * members or none: when one cannot be switched, those before it go back. After gmx_group_allreduce every member's two blocks
  * hold the whole job's per-strand totals. */
 int gmx_group_record_strands(gmx_group *g, int on);
+/* The per-site ambiguity counts on every member (gmx_engine_record_site_ambiguity; the same rule). All members or none. After
+ * gmx_group_allreduce, gmx_coverage_fetch_site_ambiguity on any member returns the group's sums, as gmx_coverage_fetch does. */
+int gmx_group_record_site_ambiguity(gmx_group *g, int on);
 /* The limit on candidates on every member (gmx_engine_set_max_candidates; the same rule). All members or none: when one refuses,
  * those before it go back to the limit they had. */
 int gmx_group_set_max_candidates(gmx_group *g, uint32_t limit);
