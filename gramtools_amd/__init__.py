@@ -15,6 +15,7 @@ from .quasimap import (  # noqa: F401
     QuasimapperGroup,
     Coverage,
     QuasimapReadsStats,
+    link_matrix,
     quasimap_reads,
     Genotyped,
     genotyping_model,

@@ -34,7 +34,7 @@ class Stats(C.Structure):
 class QueueCounts(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("mapped", "alive", "dead", "overflow_probe", "overflow_extend", "big_mapped",
                                           "cover_general", "cover_mid", "cover_overflow", "seed_cursor", "huge_search",
-                                          "inst_mapped", "huge_cover", "log_replays", "log_replayed_entries", "overflow_split")]
+                                          "inst_mapped", "huge_cover", "log_replays", "log_replayed_entries", "overflow_split", "coop_rejected")]
 
 
 class StockReport(C.Structure):
@@ -168,6 +168,10 @@ SYMBOLS = {
     "gmx_engine_record_site_ambiguity": (C.c_int, [_vp, C.c_int]),
     "gmx_engine_site_ambiguity": (C.c_int, [_vp]),
     "gmx_coverage_fetch_site_ambiguity": (C.c_int, [_vp, _u32p, _u32p, _u64]),
+    "gmx_index_link_layout": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint64), _u64]),
+    "gmx_engine_record_links": (C.c_int, [_vp, C.c_int]),
+    "gmx_engine_links": (C.c_int, [_vp]),
+    "gmx_coverage_fetch_links": (C.c_int, [_vp, _u32p, _u64]),
     "gmx_engine_set_max_candidates": (C.c_int, [_vp, C.c_uint32]),
     "gmx_engine_max_candidates": (C.c_uint32, [_vp]),
     "gmx_coverage_fetch_strand": (C.c_int, [_vp, C.c_int, _u32p, _u32p, _u32p]),
@@ -210,6 +214,7 @@ SYMBOLS = {
     "gmx_group_fetch_positions": (C.c_int, [_vp, _u64, _u64, _u32p]),
     "gmx_group_record_strands": (C.c_int, [_vp, C.c_int]),
     "gmx_group_record_site_ambiguity": (C.c_int, [_vp, C.c_int]),
+    "gmx_group_record_links": (C.c_int, [_vp, C.c_int]),
     "gmx_group_set_max_candidates": (C.c_int, [_vp, C.c_uint32]),
     "gmx_comm_unique_id": (C.c_int, [_u8p]),
     "gmx_comm_create": (C.c_int, [_u8p, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),

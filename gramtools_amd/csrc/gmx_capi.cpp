@@ -15,6 +15,7 @@
 
 #include "gmx_core.h"
 #include "gmx_internal.h"
+#include "gmx_link.h"
 
 static std::atomic<uint64_t> g_index_serial{1};
 struct gmx_index {
@@ -272,6 +273,29 @@ int gmx_index_site_layout(const gmx_index *ix, uint32_t *n_alleles, uint32_t *al
   }
   return GMX_OK;
 } GMX_GUARD_INT("gmx_index_site_layout")
+
+// The link block's layout (gmx_link.h): off[0 .. n_sites]; pure host, the engine lays its block out by the same routine
+int gmx_index_link_layout(const gmx_index *ix, int span, uint64_t *off, uint64_t n_sites_plus_1) try {
+  if (!ix || !off) {
+    gmx_set_error("gmx_index_link_layout: null argument");
+    return GMX_EINVAL;
+  }
+  const auto &h = ix->h;
+  if (h.is_nested) {
+    gmx_set_error("gmx_index_link_layout: links are recorded on flat PRGs only (the distance between two sites is not defined across the levels of a nested PRG)");
+    return GMX_EINVAL;
+  }
+  if (span < 0 || span > (int)GMX_LINK_MAX_SPAN) {
+    gmx_set_error("gmx_index_link_layout: span is 0 to " + std::to_string(GMX_LINK_MAX_SPAN) + ", not " + std::to_string(span));
+    return GMX_EINVAL;
+  }
+  if (n_sites_plus_1 != h.sites.size() + 1) {
+    gmx_set_error("gmx_index_link_layout: n_sites_plus_1 is " + std::to_string(n_sites_plus_1) + ", the index has " + std::to_string(h.sites.size()) + " sites");
+    return GMX_EINVAL;
+  }
+  gmx_link_offsets(h.sites.size(), (uint32_t)span, [&](uint64_t s) { return h.sites[s].n_alleles; }, off);
+  return GMX_OK;
+} GMX_GUARD_INT("gmx_index_link_layout")
 
 int64_t gmx_index_per_base_layout(const gmx_index *ix, uint32_t *out, uint64_t cap) try {
   const auto &h = ix->h;

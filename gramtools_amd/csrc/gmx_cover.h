@@ -29,6 +29,7 @@
 #pragma once
 #include <type_traits>
 #include "gmx_types.h"
+#include "gmx_link.h"
 
 #define GMX_RNG_LEMIRE 0    // libstdc++ >= 11 uniform_int_distribution (default: the toolchain of this image)
 #define GMX_RNG_DIVISION 1  // libstdc++ <= 10
@@ -1235,7 +1236,10 @@ GMX_HD void gmx_tally_passed(Env &env, const GmxTally &tally, uint32_t n_items) 
 template <class Env>
 GMX_HD void gmx_cover_task(const GmxIndexView &ix, Env &env, const GmxFinalState *finals, uint32_t n_final,
                            uint32_t read_len, uint32_t seed, int rng_mode, uint32_t *drawn_from = nullptr, GmxWhere *where = nullptr,
-                           uint32_t limit = 0, GmxTally *tally = nullptr) {
+                           uint32_t limit = 0, GmxTally *tally = nullptr, const GmxLinks *links = nullptr) {
+  // links (optional; nullptr or counts == nullptr: off — one uniform branch): the allele pairs of a single-instance task on a flat PRG (gmx_link.h,
+  //   DESIGN §6.6), added behind the task's record, once it has succeeded: a task that is turned away (a full log) and redone has
+  //   not counted. Tasks that leave the search as compact records never come here: gmx_link_kernel counts those.
   // tally (optional; counts == nullptr: off): the per-site ambiguity counts (GmxTally). `passed` is added at the two returns
   //   below where an ambiguous task is final and records nothing, `drawn` by gmx_class_record: never by a task that fails
   // drawn_from (optional): how many mapping instances the selection drew from (0: it did not draw), or GMX_DRAWN_LEFT_OUT: the
@@ -1255,6 +1259,8 @@ GMX_HD void gmx_cover_task(const GmxIndexView &ix, Env &env, const GmxFinalState
     }
     if (!ix.is_nested) {
       gmx_cover_single(ix, env, finals[0], read_len);
+      if (links != nullptr && links->counts != nullptr && env.status == GMX_TASK_MAPPED)
+        gmx_link_path(*links, ix, env, gmx_occ_pos(ix, finals[0].hi, finals[0].lo), finals[0].traversed, finals[0].traversing);
       return;
     }
     if (gmx_cover_single_nested(ix, env, finals[0], read_len)) return;

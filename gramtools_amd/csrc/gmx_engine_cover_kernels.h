@@ -232,7 +232,8 @@ __device__ uint32_t gmx_count_items(const GmxIndexView &ix, const GmxFinalState 
 // returns the status of the work item: MAPPED (done), OVERFLOW (the slice was too small, nothing recorded), or an error
 __device__ uint32_t gmx_tail_item(const GmxIndexView &ix, const BatchView &b, const SearchOut &o, const BigOut &g, const CoverAcc &acc,
                                   bool active, uint32_t item, uint32_t n_search, uint32_t *slice, uint64_t slice_words, bool whole_heap,
-                                  uint32_t &task_out) {
+                                  uint32_t &task_out, GmxLinks lk) {
+  const GmxLinks *links = &lk;  // (by value through the out-of-line calls, and never a pointer that may be null: either keeps the struct in scratch memory; counts == nullptr is off)
   const bool is_search = active && item < n_search;
   uint32_t task = 0, nf = 0;
   const GmxFinalState *finals = nullptr;
@@ -336,7 +337,7 @@ __device__ uint32_t gmx_tail_item(const GmxIndexView &ix, const BatchView &b, co
   uint32_t drawn_from = 0;
   GmxWhere where{0u, 0u, o.positions != nullptr};
   GmxTally tally{acc.tally(), false};
-  gmx_cover_task(ix, env, finals, nf, len, b.seeds[task >> 1], acc.rng_mode, &drawn_from, &where, acc.max_candidates, &tally);
+  gmx_cover_task(ix, env, finals, nf, len, b.seeds[task >> 1], acc.rng_mode, &drawn_from, &where, acc.max_candidates, &tally, links);
   env.log_abandon();
   if (o.positions && env.status == GMX_TASK_MAPPED) gmx_position_put(o, task, where.pos, where.n);
   if (env.status == GMX_TASK_MAPPED && is_search) {
@@ -356,7 +357,8 @@ __device__ __forceinline__ void gmx_tail_log_retry(const SearchOut &o, uint32_t 
     o.log_retry_list[atomicAdd(&o.counters[GMX_CNT_LOG_RETRY * GMX_CNT_STRIDE], 1u)] = o.cover_huge_list[item - n_search];
 }
 
-__device__ void gmx_tail_stage(const GmxIndexView &ix, const BatchView &b, const SearchOut &o, const BigOut &g, const CoverAcc &acc) {
+__device__ void gmx_tail_stage(const GmxIndexView &ix, const BatchView &b, const SearchOut &o, const BigOut &g, const CoverAcc &acc,
+                               GmxLinks lk) {
   const uint32_t n_search = o.counters[11 * GMX_CNT_STRIDE], n_cover = o.counters[15 * GMX_CNT_STRIDE];
   const uint32_t total = n_search + n_cover;
   if (total == 0) return;
@@ -369,7 +371,7 @@ __device__ void gmx_tail_stage(const GmxIndexView &ix, const BatchView &b, const
     const uint32_t item = base + lane;
     uint32_t task = 0;
     const uint32_t st = gmx_tail_item(ix, b, o, g, acc, item < total, item, n_search, acc.heap + (size_t)lane * slice_words, slice_words,
-                                      false, task);
+                                      false, task, lk);
     if (item < total && st == GMX_TASK_OVERFLOW)
       o.huge_retry[atomicAdd(&n_retry, 1u)] = item;
     else if (item < total && st == GMX_TASK_LOGFULL)
@@ -382,7 +384,7 @@ __device__ void gmx_tail_stage(const GmxIndexView &ix, const BatchView &b, const
   const uint32_t retries = n_retry;
   for (uint32_t i = 0; i < retries; ++i) {  // lane 0 alone, the whole heap
     uint32_t task = 0;
-    const uint32_t st = gmx_tail_item(ix, b, o, g, acc, lane == 0, o.huge_retry[i], n_search, acc.heap, acc.heap_words, true, task);
+    const uint32_t st = gmx_tail_item(ix, b, o, g, acc, lane == 0, o.huge_retry[i], n_search, acc.heap, acc.heap_words, true, task, lk);
     if (lane == 0 && st == GMX_TASK_LOGFULL)
       gmx_tail_log_retry(o, o.huge_retry[i], n_search);
     else if (lane == 0 && st != GMX_TASK_MAPPED && atomicCAS(&o.error[0], 0u, st) == 0u)
@@ -407,7 +409,10 @@ constexpr uint32_t gmx_cover_lds_lanes() {
 }
 template <class Env, int LIST>
 __global__ void __launch_bounds__(GMX_BLOCK) gmx_cover_kernel(GmxIndexView ix, BatchView b, SearchOut o, BigOut g,
-                                                              CoverAcc acc, uint32_t lanes_rt, uint32_t after_coop) {
+                                                              CoverAcc acc, uint32_t lanes_rt, uint32_t after_coop, GmxLinks lk) {
+  // lk: the link block and its per-site words (gmx_engine_record_links; counts == nullptr: off) — an argument of its own: CoverAcc
+  // has no padding left, and a larger one costs the last tier scratch memory (profiles/site_ambiguity/README.md)
+  const GmxLinks *links = &lk;  // (always the struct's own address: a pointer that may be null keeps it in scratch memory)
   constexpr bool BIG = LIST == 1;
   constexpr bool LDS = LIST != 1;
   const uint32_t LANES = LDS ? lanes_rt : 64u;  // active lanes of a block (blockDim.x is 64)
@@ -470,7 +475,7 @@ __global__ void __launch_bounds__(GMX_BLOCK) gmx_cover_kernel(GmxIndexView ix, B
     uint32_t drawn_from = 0;
     GmxWhere where{0u, 0u, o.positions != nullptr};
     GmxTally tally{acc.tally(), false};
-    gmx_cover_task(ix, env, finals, nf, len, b.seeds[read], acc.rng_mode, &drawn_from, &where, acc.max_candidates, &tally);
+    gmx_cover_task(ix, env, finals, nf, len, b.seeds[read], acc.rng_mode, &drawn_from, &where, acc.max_candidates, &tally, links);
     env.log_abandon();
     if (o.positions && env.status == GMX_TASK_MAPPED) gmx_position_put(o, task, where.pos, where.n);
     if (o.outcomes && env.status == GMX_TASK_MAPPED && drawn_from > 1u) gmx_outcome_selection(o, task, drawn_from);
@@ -497,7 +502,7 @@ __global__ void __launch_bounds__(GMX_BLOCK) gmx_cover_kernel(GmxIndexView ix, B
     __syncthreads();
     if (ticket == work_blocks - 1) {
       __threadfence();
-      gmx_tail_stage(ix, b, o, g, acc);
+      gmx_tail_stage(ix, b, o, g, acc, lk);
     }
   }
 }
@@ -522,7 +527,7 @@ struct OneEnv : CoverLogPart {
   __device__ __forceinline__ void sset(uint32_t w, uint32_t v) { scratch[w * GMX_ONE_THREADS] = v; }
 };
 __global__ void __launch_bounds__(GMX_ONE_THREADS) gmx_cover_one_kernel(GmxIndexView ix, BatchView b, SearchOut o, BigOut g, CoverAcc acc,
-                                                                        uint32_t enabled) {
+                                                                        uint32_t enabled, uint32_t links_on) {
   const uint32_t n = o.counters[8 * GMX_CNT_STRIDE];
   // (entry m = lane * blocks + block: a short queue — a few thousand entries among a million reads on a flat PRG — is spread
   //  over all workgroups, a handful of lanes each, instead of filling the first few waves with 64 divergent dependent-load
@@ -533,7 +538,9 @@ __global__ void __launch_bounds__(GMX_ONE_THREADS) gmx_cover_one_kernel(GmxIndex
     bool taken = false;
     if (enabled && ts.nf == 1) {
       const GmxFinalState st = ts.finals[0];
-      if (gmx_text_form(st.hi) || st.lo == st.hi) {
+      // (links recorded — gmx_engine_record_links, links_on is uniform —: a task with a path is left to the general instances, whose
+      //  gmx_cover_task adds its pairs behind the single-instance shortcut; this kernel keeps the registers it had)
+      if ((gmx_text_form(st.hi) || st.lo == st.hi) && !(links_on && st.traversed != GMX_NIL)) {
         OneEnv env;
         env.scratch = gmx_lds + threadIdx.x;
         env.arena = ts.arena;
@@ -630,7 +637,7 @@ __device__ __noinline__ void gmx_coop_passed(uint32_t *tally, uint32_t kofs, uin
 //  tried; with it the same code is allocated in 128 without a spill to scratch: profiles/max_candidates/README.md.)
 template <int LIST>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8)))
-gmx_cover_coop_kernel(GmxIndexView ix, BatchView b, SearchOut o, BigOut g, CoverAcc acc) {
+gmx_cover_coop_kernel(GmxIndexView ix, BatchView b, SearchOut o, BigOut g, CoverAcc acc, uint32_t links_on) {
   typedef typename CoopSizes<LIST>::Item CoopItemEnv;
   typedef typename CoopSizes<LIST>::Class CoopClassEnv;
   typedef GmxScratch<CoopItemEnv> SI;
@@ -683,6 +690,12 @@ gmx_cover_coop_kernel(GmxIndexView ix, BatchView b, SearchOut o, BigOut g, Cover
       w = (st.traversed != GMX_NIL || st.traversing != GMX_NIL || gmx_text_form(st.hi)) ? 1u : min(st.hi - st.lo, 16u) + 1u;
       if (o.positions) ie.sset(SI::hull(ie), gmx_text_form(st.hi) ? 1u : st.hi - st.lo + 1u);
     }
+    // Links between nearby sites (gmx_engine_record_links; links_on is wave-uniform): a task with ONE final state of
+    // ONE instance and a path is left to the serial instance of this queue, whose gmx_cover_task records it through the
+    // single-instance shortcut and adds its pairs there — this kernel would record it without ever seeing its path as a list.
+    if (links_on)
+      rejected = rejected || (((uint32_t)(__ballot(have && ts.nf == 1u && gl == 0u && st.traversed != GMX_NIL &&
+                                                   (gmx_text_form(st.hi) || st.lo == st.hi)) >> gbase) & 0xFFFFu) != 0u);
     uint32_t incl = w;
 #pragma unroll
     for (uint32_t d = 1; d < 16; d <<= 1) {
@@ -990,6 +1003,51 @@ __global__ void __launch_bounds__(GMX_BLOCK) gmx_cover_single_rest_kernel(GmxInd
   const uint32_t n = o.counters[GMX_CNT_SINGLE_REST * GMX_CNT_STRIDE];
   for (uint32_t i = blockIdx.x * GMX_BLOCK + threadIdx.x; i < n; i += gridDim.x * GMX_BLOCK)
     gmx_cover_single_rec<false>(ix, o, acc, o.single_rest_list[i], o.cover_general_list, 8u);
+}
+
+// Links between nearby sites (gmx_engine_record_links, gmx_link.h): one lane per compact record over the same eight region queues,
+// so a workgroup's atomics land in the L2 of the XCD that serves that stretch of sites. Every compact record is a final, mapped
+// task with ONE mapping instance (finish_lane: one text-form state), and the coverage kernels never turn one away for good — what
+// gmx_cover_jump_kernel declines, gmx_cover_single_rest_kernel records; what finds the log full, the replay records — so each
+// record counts here once, whatever they do with it afterwards. No LDS; launched only when recording is on.
+// (The record's words as VALUES: 64-bit shifts pick an allele or a site. With CompactEnv's chains of selects between neighbouring
+//  members the compiler indexed the record in memory and moved all 80 bytes of the Env to LDS, 20 KB per workgroup.)
+struct LinkRecEnv {
+  uint64_t lo, hi;  // run form: allele h is byte h of hi:lo; three-site form: lo = a0 | a1 << 16 | a2 << 32, hi = s0 | s1 << 32
+  uint32_t s0, s2, n;
+  bool run;
+  __device__ __forceinline__ uint32_t h_site(uint32_t h) const {
+    if (h & GMX_INLINE_FLAG) return 5u + 2u * (h & ~GMX_INLINE_FLAG);
+    if (run) return s0 + 2u * h;
+    return h < 2u ? (uint32_t)(hi >> (32u * h)) : s2;
+  }
+  __device__ __forceinline__ int32_t h_allele(uint32_t h) const {
+    if (h & GMX_INLINE_FLAG) return -1;
+    if (run) return (int32_t)(((h < 8u ? lo : hi) >> (8u * (h & 7u))) & 0xFFull);
+    return (int32_t)((lo >> (16u * h)) & (h < 2u ? 0xFFFFull : 0xFFFFFFFFull));
+  }
+  __device__ __forceinline__ uint32_t h_next(uint32_t h) const {
+    if (h & GMX_INLINE_FLAG) return GMX_NIL;
+    return h + 1 < n ? h + 1 : GMX_NIL;
+  }
+};
+__global__ void __launch_bounds__(GMX_BLOCK) gmx_link_kernel(GmxIndexView ix, SearchOut o, GmxLinks lk) {
+  const uint32_t region = blockIdx.x & (GMX_REGIONS - 1);
+  const uint32_t n_mapped = o.counters[(16 + region) * GMX_CNT_STRIDE];
+  const uint32_t m = (blockIdx.x / GMX_REGIONS) * GMX_BLOCK + threadIdx.x;
+  if (m >= n_mapped) return;
+  const GmxCoverRec r = o.cover_recs[(size_t)region * o.region_cap + m];
+  const uint32_t n = (r.len_n >> 16) & 31u, s0 = r.site[0], s1 = r.site[1], s2 = r.site[2], a01 = r.a01, a2 = r.a2;
+  if (n + (r.tvg != GMX_NIL ? 1u : 0u) < 2u) return;  // fewer than two loci: nothing to fetch
+  const bool run = (r.len_n & GMX_REC_RUN_FLAG) != 0;
+  LinkRecEnv env;
+  env.lo = run ? ((uint64_t)s1 | ((uint64_t)s2 << 32)) : ((uint64_t)a01 | ((uint64_t)a2 << 32));
+  env.hi = run ? ((uint64_t)a01 | ((uint64_t)a2 << 32)) : ((uint64_t)s0 | ((uint64_t)s1 << 32));
+  env.s0 = s0;
+  env.s2 = s2;
+  env.n = n;
+  env.run = run;
+  gmx_link_path(lk, ix, env, r.p, 0u, r.tvg);
 }
 
 // ---- grouped log full: the batch's failed entries again, after the host has drained the log (launch_log_replay) ----

@@ -89,6 +89,23 @@ struct gmx_engine {
     const gmx_engine *w = owner ? owner : this;
     return w->record_site_ambiguity ? (w->record_strands ? 2 : 1) * n_acc : 0;
   }
+  // Links between nearby sites (gmx_engine_record_links; gmx_link.h): n_links words rounded up to 64, inside the fused
+  // block behind the tally — [block | (reverse block) | tally | links | limbs] — so the resets and the exchange carry them too.
+  // d_link_sites: the device-only table of per-site words, built when the switch is turned on. link_span 0: off. The twin reads its
+  // owner's switch, table and sizes.
+  int link_span = 0;
+  size_t n_links = 0;        // words of the layout (off[n_sites]); the block holds them rounded up to 64
+  GmxLinkSite *d_link_sites = nullptr;
+  std::vector<uint8_t> link_alleles;  // per site: A'(s) (gmx_link_alleles of its allele count), kept from the host index
+  size_t links_off() const {  // words from d_fused to the link block; 0: off
+    const gmx_engine *w = owner ? owner : this;
+    return w->link_span ? (w->record_strands ? 2 : 1) * n_acc + w->n_tally : 0;
+  }
+  GmxLinks links() const {  // a kernel argument of its own (CoverAcc has no padding left); counts == nullptr: off
+    const gmx_engine *w = owner ? owner : this;
+    if (!w->link_span) return GmxLinks{nullptr, nullptr, 0u, 0u};
+    return GmxLinks{w->d_link_sites, d_fused + links_off(), (uint32_t)w->link_span, dview.n_sites};
+  }
   // The limit on a selection's candidates (gmx_engine_set_max_candidates; 0: none). Like record_strands it changes
   // only while nothing is recorded, and the twin reads its owner's: a replay or the second workspace meets the first pass's value.
   uint32_t max_candidates = 0;
@@ -406,14 +423,14 @@ static void launch_cover_lds(gmx_engine *e, hipStream_t stream, const BatchView 
   const size_t lds = (size_t)GmxScratchFixed<Env>::total * lanes * sizeof(uint32_t);
   const uint32_t per_cu = std::min<uint32_t>((uint32_t)(160 * 1024 / lds), 32u);
   hipLaunchKernelGGL((gmx_cover_kernel<Env, LIST>), dim3(e->n_cus * per_cu), dim3(64), lds, stream, e->dview, b, o, e->big,
-                     acc, lanes, after_coop ? 1u : 0u);
+                     acc, lanes, after_coop ? 1u : 0u, e->links());
 }
 
 template <int LIST>
 static void launch_cover_coop(gmx_engine *e, hipStream_t stream, const BatchView &b, const SearchOut &o, const CoverAcc &acc) {
   const size_t lds = (size_t)gmx_coop_lds_words<LIST>() * sizeof(uint32_t);
   const uint32_t per_cu = std::min<uint32_t>((uint32_t)(160 * 1024 / lds), 16u);
-  hipLaunchKernelGGL((gmx_cover_coop_kernel<LIST>), dim3(e->n_cus * per_cu), dim3(64), lds, stream, e->dview, b, o, e->big, acc);
+  hipLaunchKernelGGL((gmx_cover_coop_kernel<LIST>), dim3(e->n_cus * per_cu), dim3(64), lds, stream, e->dview, b, o, e->big, acc, e->links().counts ? 1u : 0u);
 }
 
 extern "C" {
@@ -528,6 +545,7 @@ static void gmx_dev_index_release(GmxDeviceIndex *d) {
 static int engine_create(const gmx_index *ixh, const gmx_engine_opts *opts_in, gmx_engine *primary, gmx_engine **out);
 static int set_record_strands(gmx_engine *e, bool on);
 static int set_record_site_ambiguity(gmx_engine *e, bool on);
+static int set_record_links(gmx_engine *e, int span);
 int gmx_engine_create(const gmx_index *ixh, const gmx_engine_opts *opts_in, gmx_engine **out) try {
   int rc = engine_create(ixh, opts_in, nullptr, out);
   if (rc) return rc;
@@ -559,6 +577,13 @@ int gmx_engine_create(const gmx_index *ixh, const gmx_engine_opts *opts_in, gmx_
   // MEASUREMENT HOOK ONLY (profiles/site_ambiguity: the cost of the per-site counts in an unchanged benchmark): nothing reads them
   if (const char *sa = getenv("GMX_RECORD_SITE_AMBIGUITY"))
     if (atoi(sa) != 0 && (rc = set_record_site_ambiguity(e, true))) {
+      gmx_engine_destroy(e);
+      *out = nullptr;
+      return rc;
+    }
+  // MEASUREMENT HOOK ONLY (profiles/site_links: the cost of the links in an unchanged benchmark; flat PRGs): nothing reads them
+  if (const char *ls = getenv("GMX_RECORD_LINKS"))
+    if (atoi(ls) != 0 && !e->dview.is_nested && (rc = set_record_links(e, atoi(ls)))) {
       gmx_engine_destroy(e);
       *out = nullptr;
       return rc;
@@ -681,6 +706,10 @@ static int engine_create(const gmx_index *ixh, const gmx_engine_opts *opts_in, g
   // The grouped log is used only by sites with more alleles than get dense group counters (gmx_index.cpp: 8). Between
   // batches the engine looks at its real fill (log_settle): drained when half full; entries that found it full are redone.
   for (const GmxSite &st : h.sites) e->log_sites = e->log_sites || st.grouped_off == GMX_GROUPED_LOG;
+  if (!primary && !h.is_nested) {  // what gmx_engine_record_links lays the link block out from (flat PRGs only)
+    e->link_alleles.resize(h.sites.size());
+    for (size_t s = 0; s < h.sites.size(); ++s) e->link_alleles[s] = (uint8_t)gmx_link_alleles(h.sites[s].n_alleles);
+  }
   {  // the lean single-instance coverage kernel where most sites have geometry records (GMX_NO_COVER_JUMP: A/B runs)
     uint64_t n_jump = 0;
     for (const GmxSiteGeo &g : h.site_geo) n_jump += (g.flags & GMX_SITE_JUMP) ? 1u : 0u;
@@ -988,7 +1017,7 @@ static int launch_log_replay(gmx_engine *e, hipStream_t stream) {
     hipLaunchKernelGGL(gmx_cover_single_replay_kernel<false>, dim3(e->n_cus * 4), dim3(GMX_BLOCK), 0, stream, e->dview, e->last_b, o, e->last_acc,
                      e->d_log_retry_recs[in]);
   hipLaunchKernelGGL((gmx_cover_kernel<CoverEnvBig, 1>), dim3(e->cover_big_lanes / 64), dim3(64), e->last_big_lds, stream, e->dview,
-                     e->last_b, o, e->big, e->last_acc, 64u, 0u);
+                     e->last_b, o, e->big, e->last_acc, 64u, 0u, e->links());
   HIP_TRY(hipGetLastError());
   e->log_retry_side = out;
   e->last_o.log_retry_list = o.log_retry_list;
@@ -1302,10 +1331,14 @@ static int launch_batch(gmx_engine *e, const BatchInput &in, hipStream_t stream)
   // the large-capacity pass's chain of few-lane kernels: with reads in repeats that chain is the batch's longest path)
   const bool general_on_side = !e->dview.is_nested;
   HIP_TRY(hipStreamWaitEvent(e->side_stream, e->ev_fork2, 0));
+  // links between nearby sites (gmx_engine_record_links): the region queues are complete behind the extend kernel's last pass —
+  // one lane per compact record on side 1, beside the single-instance kernel on the main stream; joined through ev_filter below
+  if (const GmxLinks lk = e->links(); lk.counts)
+    hipLaunchKernelGGL(gmx_link_kernel, dim3(task_grid.x * GMX_REGIONS), dim3(GMX_BLOCK), 0, e->side_stream, e->dview, o, lk);
   const size_t one_lds = (size_t)4 * GMX_WIDE_LOCI * GMX_ONE_THREADS * sizeof(uint32_t);
   const bool one = !getenv("GMX_NO_COVER_ONE");
   auto launch_one = [&](hipStream_t st) {  // (with GMX_NO_COVER_ONE the kernel only passes its queue on: A/B runs)
-    hipLaunchKernelGGL(gmx_cover_one_kernel, dim3(e->n_cus * 4), dim3(GMX_ONE_THREADS), one_lds, st, e->dview, b, o, e->big, acc, one ? 1u : 0u);
+    hipLaunchKernelGGL(gmx_cover_one_kernel, dim3(e->n_cus * 4), dim3(GMX_ONE_THREADS), one_lds, st, e->dview, b, o, e->big, acc, one ? 1u : 0u, e->links().counts ? 1u : 0u);
   };
   if (general_on_side) {
     launch_one(e->side_stream);
@@ -1345,7 +1378,7 @@ static int launch_batch(gmx_engine *e, const BatchInput &in, hipStream_t stream)
   }
   HIP_TRY(hipStreamWaitEvent(last, e->ev_filter, 0));
   hipLaunchKernelGGL((gmx_cover_kernel<CoverEnvBig, 1>), dim3(e->cover_big_lanes / 64), dim3(64), big_lds, last, e->dview,
-                     b, o, e->big, acc, 64u, 0u);
+                     b, o, e->big, acc, 64u, 0u, e->links());
   if (general_on_side) {
     HIP_TRY(hipEventRecord(e->ev_join, e->side2_stream));
     HIP_TRY(hipStreamWaitEvent(stream, e->ev_join, 0));
@@ -2075,6 +2108,7 @@ int gmx_engine_queue_counts(gmx_engine *e, gmx_queue_counts *out) try {
   out->log_replays = e->log_replays;
   out->log_replayed_entries = e->log_replayed_entries;
   out->overflow_split = c(29);
+  out->coop_rejected = c(26) + c(27) + c(28);
   return GMX_OK;
 } GMX_GUARD_INT("gmx_engine_queue_counts")
 
@@ -2206,11 +2240,37 @@ int gmx_coverage_fetch_strand(gmx_engine *e, int strand, uint32_t *allele_sum, u
 // The engine's one-block or two-block allocation. Nothing is recorded and nothing is in flight when this runs, so the new
 // block is simply a zeroed one; the old one stays untouched until the new one exists.
 // Layout of the fused block: [block] or [forward block | reverse block], then [tally: 2 * n_sites words rounded up to 64] when the
-// per-site ambiguity counts are on, then the 32 limb words; 16 words of read counters and the log cursor behind it.
-static int set_block_layout(gmx_engine *e, bool strands, bool site_ambiguity, const char *who) {
-  if (e->record_strands == strands && e->record_site_ambiguity == site_ambiguity) return GMX_OK;
+// per-site ambiguity counts are on, then [links: off[n_sites] words rounded up to 64] when links are recorded, then the 32 limb
+// words; 16 words of read counters and the log cursor behind it.
+static int set_block_layout(gmx_engine *e, bool strands, bool site_ambiguity, int span, const char *who) {
+  if (e->record_strands == strands && e->record_site_ambiguity == site_ambiguity && e->link_span == span) return GMX_OK;
   const size_t n_tally = site_ambiguity ? (2 * (size_t)e->dview.n_sites + 63) / 64 * 64 : 0;
-  const size_t n_fused = (strands ? 2 : 1) * e->n_acc + n_tally + 32;
+  // the link block (gmx_link.h): its size and the per-site words follow from the index and the span alone — one scan of the sites
+  size_t n_links = 0;
+  std::vector<GmxLinkSite> table;
+  if (span) {
+    if (e->dview.is_nested) {
+      gmx_set_error(std::string(who) + ": links are recorded on flat PRGs only (the distance between two sites is not defined across the levels of a nested PRG)");
+      return GMX_EINVAL;
+    }
+    const size_t n_sites = e->link_alleles.size();
+    std::vector<uint64_t> off(n_sites + 1);
+    gmx_link_offsets(n_sites, (uint32_t)span, [&](uint64_t s) { return (uint32_t)e->link_alleles[s]; }, off.data());
+    if (off[n_sites] > 0xFFFFFFFFull) {
+      gmx_set_error(std::string(who) + ": the link block of this index and span exceeds 2^32 words");
+      return GMX_EINVAL;
+    }
+    n_links = (size_t)off[n_sites];
+    if (span != e->link_span) {
+      table.resize(n_sites);
+      for (size_t s = 0; s < n_sites; ++s) {
+        uint32_t f = 0;
+        for (size_t k = 0; k < 8 && s + k < n_sites; ++k) f |= (uint32_t)e->link_alleles[s + k] << (4 * k);
+        table[s] = GmxLinkSite{(uint32_t)off[s], f};
+      }
+    }
+  }
+  const size_t n_fused = (strands ? 2 : 1) * e->n_acc + n_tally + (n_links + 63) / 64 * 64 + 32;
   if (n_fused + 32 > 0xFFFFFFFFull) {  // (the resets' word counts and CoverAcc::rev_off are 32 bits)
     gmx_set_error(std::string(who) + ": the accumulator blocks of this index exceed 2^32 words");
     return GMX_EINVAL;
@@ -2218,10 +2278,27 @@ static int set_block_layout(gmx_engine *e, bool strands, bool site_ambiguity, co
   uint32_t *old = e->d_fused, *q = nullptr;
   int rc = e->alloc(&q, n_fused + 32, true);  // + 16 words of read counters + log cursor
   if (rc) return rc;
+  GmxLinkSite *old_sites = e->d_link_sites, *sites = span == e->link_span ? old_sites : nullptr;
+  if (span && span != e->link_span) {  // (the old block and mode stay when this fails)
+    rc = e->alloc(&sites, table.size(), false);
+    if (!rc && !table.empty() && hipMemcpy(sites, table.data(), table.size() * sizeof(GmxLinkSite), hipMemcpyHostToDevice) != hipSuccess) {
+      gmx_set_error(std::string(who) + ": the per-site words could not be copied to the device");
+      rc = GMX_EHIP;
+    }
+    if (rc) {
+      e->release(sites);
+      e->release(q);
+      return rc;
+    }
+  }
   e->release(old);
+  if (sites != old_sites) e->release(old_sites);
   e->record_strands = strands;
   e->record_site_ambiguity = site_ambiguity;
   e->n_tally = n_tally;
+  e->link_span = span;
+  e->n_links = n_links;
+  e->d_link_sites = sites;
   e->reset_pending = false;  // (a queued reset: the fresh block is zero)
   for (gmx_engine *w : {e, e->twin}) {  // the twin's alias of the block and every derived pointer follow
     if (!w) continue;
@@ -2233,13 +2310,20 @@ static int set_block_layout(gmx_engine *e, bool strands, bool site_ambiguity, co
   }
   return GMX_OK;
 }
-static int set_record_strands(gmx_engine *e, bool on) { return set_block_layout(e, on, e->record_site_ambiguity, "gmx_engine_record_strands"); }
+static int set_record_strands(gmx_engine *e, bool on) { return set_block_layout(e, on, e->record_site_ambiguity, e->link_span, "gmx_engine_record_strands"); }
 static int set_record_site_ambiguity(gmx_engine *e, bool on) {
-  return set_block_layout(e, e->record_strands, on, "gmx_engine_record_site_ambiguity");
+  return set_block_layout(e, e->record_strands, on, e->link_span, "gmx_engine_record_site_ambiguity");
+}
+static int set_record_links(gmx_engine *e, int span) {
+  if (span < 0 || span > (int)GMX_LINK_MAX_SPAN) {
+    gmx_set_error("gmx_engine_record_links: span is 0 (off) to " + std::to_string(GMX_LINK_MAX_SPAN) + ", not " + std::to_string(span));
+    return GMX_EINVAL;
+  }
+  return set_block_layout(e, e->record_strands, e->record_site_ambiguity, span, "gmx_engine_record_links");
 }
 
 // The C ABI of a switch of the block's layout: only while nothing is recorded
-static int block_layout_switch(gmx_engine *e, int (*set)(gmx_engine *, bool), int on, const char *who) {
+static int block_layout_switch(gmx_engine *e, int (*set)(gmx_engine *, int), int arg, const char *who) {
   if (!e) {
     gmx_set_error("null engine");
     return GMX_EINVAL;
@@ -2250,15 +2334,15 @@ static int block_layout_switch(gmx_engine *e, int (*set)(gmx_engine *, bool), in
   }
   HIP_TRY(hipSetDevice(e->opts.device));
   HIP_TRY(hipDeviceSynchronize());  // the engine's work (a reset still queued is dropped: the fresh block is zero)
-  return set(e, on != 0);
+  return set(e, arg);
 }
 
 int gmx_engine_record_strands(gmx_engine *e, int on) try {
-  return block_layout_switch(e, set_record_strands, on, "gmx_engine_record_strands");
+  return block_layout_switch(e, [](gmx_engine *w, int v) { return set_record_strands(w, v != 0); }, on, "gmx_engine_record_strands");
 } GMX_GUARD_INT("gmx_engine_record_strands")
 
 int gmx_engine_record_site_ambiguity(gmx_engine *e, int on) try {
-  return block_layout_switch(e, set_record_site_ambiguity, on, "gmx_engine_record_site_ambiguity");
+  return block_layout_switch(e, [](gmx_engine *w, int v) { return set_record_site_ambiguity(w, v != 0); }, on, "gmx_engine_record_site_ambiguity");
 } GMX_GUARD_INT("gmx_engine_record_site_ambiguity")
 
 int gmx_engine_site_ambiguity(gmx_engine *e) try {
@@ -2290,6 +2374,37 @@ int gmx_coverage_fetch_site_ambiguity(gmx_engine *e, uint32_t *drawn, uint32_t *
   }
   return GMX_OK;
 } GMX_GUARD_INT("gmx_coverage_fetch_site_ambiguity")
+
+// Links between nearby sites: the switch follows the rule of the two above; the span is the mode.
+int gmx_engine_record_links(gmx_engine *e, int span) try {
+  return block_layout_switch(e, set_record_links, span, "gmx_engine_record_links");
+} GMX_GUARD_INT("gmx_engine_record_links")
+
+int gmx_engine_links(gmx_engine *e) try {
+  return e ? e->link_span : 0;
+} GMX_GUARD_ZERO("gmx_engine_links")
+
+int gmx_coverage_fetch_links(gmx_engine *e, uint32_t *words, uint64_t n_words) try {
+  if (!e || (n_words && !words)) {
+    gmx_set_error("gmx_coverage_fetch_links: null argument");
+    return GMX_EINVAL;
+  }
+  if (!e->link_span) {
+    gmx_set_error("gmx_coverage_fetch_links: the engine does not record them (gmx_engine_record_links)");
+    return GMX_EINVAL;
+  }
+  if (n_words != e->n_links) {
+    gmx_set_error("gmx_coverage_fetch_links: n_words is " + std::to_string(n_words) + ", the layout of this index and span has " + std::to_string(e->n_links) +
+                  " (gmx_index_link_layout)");
+    return GMX_EINVAL;
+  }
+  {  // (a task redone after a full log counts then; both workspaces' streams)
+    int rc = fetch_blocks(e, 0, 0, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+  }
+  if (n_words) HIP_TRY(hipMemcpy(words, e->d_fused + e->links_off(), (size_t)n_words * 4, hipMemcpyDeviceToHost));
+  return GMX_OK;
+} GMX_GUARD_INT("gmx_coverage_fetch_links")
 
 // The limit on a selection's candidates: a launch argument of the coverage kernels (CoverAcc::max_candidates), nothing to allocate.
 // Only while nothing is recorded: the coverage of one job is that of ONE limit, and a task redone after a full log or run on the
@@ -2465,6 +2580,7 @@ void gmx_engine_raw(gmx_engine *e, GmxEngineRaw *out) {
   out->log_sites = e->log_sites;
   out->record_strands = e->record_strands;
   out->record_site_ambiguity = e->record_site_ambiguity;
+  out->link_span = e->link_span;
 }
 
 int gmx_engine_log_export(gmx_engine *e, std::vector<uint32_t> &out) {

@@ -40,6 +40,7 @@ struct GmxEngineRaw {
   bool log_sites;     // the index has sites that use the grouped log
   bool record_strands;  // two blocks (gmx_engine_record_strands): d_fused and n_fused change with it — take a fresh copy before an exchange
   bool record_site_ambiguity;  // the per-site ambiguity counts inside the block (gmx_engine_record_site_ambiguity): the same holds
+  int link_span;               // the link block inside the block (gmx_engine_record_links; 0: off): the same holds
 };
 void gmx_engine_raw(gmx_engine *e, GmxEngineRaw *out);
 uint64_t gmx_engine_reset_epoch(const gmx_engine *e);  // resets of the per-read logs so far (gmx_group's ledgers)

@@ -597,8 +597,13 @@ int gmx_group_allreduce(gmx_group *g) try {
   for (auto &m : g->ms) {
     int rc = gmx_engine_sync(m.e);
     if (rc) return rc;
-    gmx_engine_raw(m.e, &m.raw);  // (gmx_engine_record_strands and gmx_engine_record_site_ambiguity replace the block)
+    gmx_engine_raw(m.e, &m.raw);  // (gmx_engine_record_strands, gmx_engine_record_site_ambiguity and gmx_engine_record_links replace the block)
   }
+  for (auto &m : g->ms)
+    if (m.raw.link_span != g->ms[0].raw.link_span) {
+      gmx_set_error("gmx_group_allreduce: the members disagree on the span of the links (gmx_group_record_links sets all of them)");
+      return GMX_EINVAL;
+    }
   for (auto &m : g->ms)
     if (m.raw.record_strands != g->ms[0].raw.record_strands || m.raw.record_site_ambiguity != g->ms[0].raw.record_site_ambiguity ||
         m.raw.n_fused != g->ms[0].raw.n_fused) {
@@ -616,8 +621,8 @@ int gmx_group_allreduce(gmx_group *g) try {
   return GMX_OK;
 } GMX_GUARD_INT("gmx_group_allreduce")
 
-// A switch of the members' block layout (per-strand blocks, per-site ambiguity counts): all members or none
-static int group_layout_switch(gmx_group *g, int (*set)(gmx_engine *, int), bool GmxEngineRaw::*field, int on) {
+// A switch of the members' block layout (per-strand blocks, per-site ambiguity counts, links): all members or none
+static int group_layout_switch(gmx_group *g, int (*set)(gmx_engine *, int), int (*was)(const GmxEngineRaw &), int on) {
   if (!g || g->ms.empty()) {
     gmx_set_error("null group");
     return GMX_EINVAL;
@@ -627,7 +632,7 @@ static int group_layout_switch(gmx_group *g, int (*set)(gmx_engine *, int), bool
     const int rc = set(g->ms[i].e, on);
     if (rc) {  // all or none: the members before go back to what they recorded
       for (size_t j = 0; j < i; ++j) {
-        (void)set(g->ms[j].e, g->ms[j].raw.*field ? 1 : 0);
+        (void)set(g->ms[j].e, was(g->ms[j].raw));  // (a switch: 0 / 1; the links: their span)
         gmx_engine_raw(g->ms[j].e, &g->ms[j].raw);
       }
       return rc;
@@ -638,12 +643,16 @@ static int group_layout_switch(gmx_group *g, int (*set)(gmx_engine *, int), bool
 }
 
 int gmx_group_record_strands(gmx_group *g, int on) try {
-  return group_layout_switch(g, gmx_engine_record_strands, &GmxEngineRaw::record_strands, on);
+  return group_layout_switch(g, gmx_engine_record_strands, [](const GmxEngineRaw &r) { return r.record_strands ? 1 : 0; }, on);
 } GMX_GUARD_INT("gmx_group_record_strands")
 
 int gmx_group_record_site_ambiguity(gmx_group *g, int on) try {
-  return group_layout_switch(g, gmx_engine_record_site_ambiguity, &GmxEngineRaw::record_site_ambiguity, on);
+  return group_layout_switch(g, gmx_engine_record_site_ambiguity, [](const GmxEngineRaw &r) { return r.record_site_ambiguity ? 1 : 0; }, on);
 } GMX_GUARD_INT("gmx_group_record_site_ambiguity")
+
+int gmx_group_record_links(gmx_group *g, int span) try {
+  return group_layout_switch(g, gmx_engine_record_links, [](const GmxEngineRaw &r) { return r.link_span; }, span);
+} GMX_GUARD_INT("gmx_group_record_links")
 
 int gmx_group_set_max_candidates(gmx_group *g, uint32_t limit) try {
   if (!g || g->ms.empty()) {

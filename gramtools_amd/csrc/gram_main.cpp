@@ -113,7 +113,14 @@ const char *kGenotypeHelp =
     "                              orientations that recorded no variant-site placement, left out by --max_candidates or drawn\n"
     "                              outside every site (outermost sites only) — and genotype_dir/site_ambiguity.json: sites,\n"
     "                              sites_drawn, sites_passed_over, drawn, passed_over. genotyped.json and genotyped.vcf.gz gain\n"
-    "                              AMB_DRAWN and AMB_PASSED per site (the last two FORMAT fields, `.:.` at a null call)\n";
+    "                              AMB_DRAWN and AMB_PASSED per site (the last two FORMAT fields, `.:.` at a null call)\n"
+    "  --site_links arg            links between nearby sites (engine extension; flat PRGs): D in 1..7. For every read orientation\n"
+    "                              that maps with exactly one mapping instance, count the allele pairs it shows at sites at most D\n"
+    "                              site indices apart (sites of at most 8 alleles). Writes coverage/site_links.json,\n"
+    "                              {\"span\":D,\"links\":[[s,t,[[row]...]],...]}: one entry per pair of sites s < t with a non-zero\n"
+    "                              count, ascending, rows by the allele at s, columns by the allele at t (0-based, the order of\n"
+    "                              allele_sum_coverage) — and genotype_dir/site_links.json: span, sites, linkable_sites,\n"
+    "                              pairs_with_count, count. The calls do not change\n";
 
 [[noreturn]] void die(const std::string &msg, int code = 1) {
   std::cout << msg << std::endl;
@@ -1451,6 +1458,13 @@ int run_genotype(const Args &a) {
     if (n < 1 || n > 0xFFFFFFFFull) die("--max_candidates takes a whole number >= 1 (got '" + v + "')");
     max_candidates = (uint32_t)n;
   }
+  // --site_links D: the engines' links between nearby sites (gmx_group_record_links), D in 1..7
+  int site_links = 0;
+  if (a.has("site_links")) {
+    const std::string v = a.one("site_links");
+    if (v.size() != 1 || v[0] < '1' || v[0] > '7') die("--site_links takes a span of 1 to 7 sites (got '" + v + "')");
+    site_links = v[0] - '0';
+  }
   for (auto const &smp : samples) {
     mkdirs(join(smp.run_dir, "coverage"));
     mkdirs(join(smp.run_dir, "genotype"));
@@ -1576,6 +1590,7 @@ int run_genotype(const Args &a) {
   // --site_ambiguity: the engines' per-site counts (gmx_group_record_site_ambiguity), across samples (a reset zeroes them, the mode stays)
   const bool site_ambiguity = a.has("site_ambiguity");
   if (site_ambiguity) GMX_CHECK(gmx_group_record_site_ambiguity(grp, 1));
+  if (site_links) GMX_CHECK(gmx_group_record_links(grp, site_links));  // (a nested PRG: the engine's message; a reset between samples keeps the span)
   if (max_candidates) GMX_CHECK(gmx_group_set_max_candidates(grp, max_candidates));  // before the first reads file; a reset between samples keeps it
   auto note_outcomes = [&](int engine, uint64_t n) {  // BEFORE the call that hands n reads to `engine` (or to the group)
     if (n == 0) return;
@@ -1863,6 +1878,53 @@ int run_genotype(const Args &a) {
       std::ofstream o(path);
       o << "{\"sites\":" << info.n_sites << ",\"sites_drawn\":" << sites_drawn << ",\"sites_passed_over\":" << sites_passed
         << ",\"drawn\":" << sum_drawn << ",\"passed_over\":" << sum_passed << "}\n";
+      close_checked(o, path);
+    }
+  }
+
+  if (site_links) {  // --site_links: the job's sums (the exchange carried them with the coverage)
+    std::vector<uint32_t> n_al(std::max<uint32_t>(info.n_sites, 1), 0);
+    GMX_CHECK(gmx_index_site_layout(ix, n_al.data(), nullptr, nullptr, nullptr, nullptr));
+    std::vector<uint64_t> off((size_t)info.n_sites + 1, 0);
+    GMX_CHECK(gmx_index_link_layout(ix, site_links, off.data(), (uint64_t)info.n_sites + 1));
+    std::vector<uint32_t> words(std::max<uint64_t>(off[info.n_sites], 1), 0);
+    GMX_CHECK(gmx_coverage_fetch_links(eng, words.data(), off[info.n_sites]));
+    auto linkable = [&](uint64_t s) -> uint32_t { return s < info.n_sites && n_al[s] <= 8 ? n_al[s] : 0u; };
+    uint64_t n_linkable = 0, n_pairs = 0, sum = 0;
+    for (uint32_t s = 0; s < info.n_sites; ++s) n_linkable += linkable(s) != 0;
+    {  // coverage/site_links.json
+      const std::string path = join(cov_dir, "site_links.json");
+      std::ofstream o(path);
+      o << "{\"span\":" << site_links << ",\"links\":[";
+      for (uint32_t s = 0; s < info.n_sites; ++s) {
+        uint64_t at = off[s];
+        const uint32_t rows = linkable(s);
+        for (int d = 1; d <= site_links && rows; ++d) {
+          const uint32_t cols = linkable((uint64_t)s + d);
+          uint64_t m_sum = 0;
+          for (uint64_t i = 0; i < (uint64_t)rows * cols; ++i) m_sum += words[at + i];
+          if (m_sum) {
+            o << (n_pairs ? "," : "") << "[" << s << "," << s + d << ",[";
+            for (uint32_t r = 0; r < rows; ++r) {
+              o << (r ? "," : "") << "[";
+              for (uint32_t c = 0; c < cols; ++c) o << (c ? "," : "") << words[at + (uint64_t)r * cols + c];
+              o << "]";
+            }
+            o << "]]";
+            ++n_pairs;
+            sum += m_sum;
+          }
+          at += (uint64_t)rows * cols;
+        }
+      }
+      o << "]}\n";
+      close_checked(o, path);
+    }
+    {  // G/site_links.json
+      const std::string path = join(run_dir, "site_links.json");
+      std::ofstream o(path);
+      o << "{\"span\":" << site_links << ",\"sites\":" << info.n_sites << ",\"linkable_sites\":" << n_linkable << ",\"pairs_with_count\":" << n_pairs
+        << ",\"count\":" << sum << "}\n";
       close_checked(o, path);
     }
   }

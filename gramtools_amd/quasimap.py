@@ -222,6 +222,13 @@ class Index:
         self.lib.gmx_index_per_base_layout(self.h, _p(out, C.c_uint32), n)
         return out[:n]
 
+    def link_layout(self, span: int) -> np.ndarray:
+        """``off[0 .. n_sites]`` of the link block for ``span`` (gmx_index_link_layout; see Quasimapper.record_links): site s's
+        matrices start at word off[s], off[n_sites] is the block's size. Flat PRGs only, span 0..7."""
+        off = np.zeros(self.n_sites + 1, dtype=np.uint64)
+        check(self.lib.gmx_index_link_layout(self.h, int(span), _p(off, C.c_uint64), self.n_sites + 1))
+        return off
+
     def allele_base_layout(self):
         off = np.zeros(self.info.n_allele_slots, dtype=np.uint32)
         ln = np.zeros(self.info.n_allele_slots, dtype=np.uint32)
@@ -300,6 +307,18 @@ class Index:
     def jump_states(self, lo, hi):
         """search_state_vBWT_jumps of the path-less state [lo, hi] (vBWT_jump.cpp:134-183)."""
         return self._unpack_states(self._states_call(self.lib.gmx_index_jump_states, lo, hi))
+
+
+def link_matrix(n_alleles, off, words, s: int, d: int) -> np.ndarray:
+    """M(s, d) of a link block as a 2-D array ``[allele at s][allele at s + d]`` — ``n_alleles``: Index.n_alleles, ``off, words``:
+    Quasimapper.links(). A pair of sites without a matrix (an end with more than 8 alleles or past the last site, d beyond the
+    recorded span) gives an array with no element."""
+    a = lambda t: int(n_alleles[t]) if 0 <= t < len(n_alleles) and int(n_alleles[t]) <= 8 else 0
+    rows, cols = a(s), a(s + d)
+    start = int(off[s]) + rows * sum(a(s + e) for e in range(1, d)) if 0 <= s < len(n_alleles) else 0
+    if d < 1 or rows == 0 or cols == 0 or start + rows * cols > int(off[s + 1]):
+        return np.zeros((0, 0), dtype=np.uint32)
+    return np.asarray(words[start:start + rows * cols], dtype=np.uint32).reshape(rows, cols)
 
 
 @dataclass
@@ -596,6 +615,26 @@ class Quasimapper:
         drawn, passed = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
         check(self.lib.gmx_coverage_fetch_site_ambiguity(self.h, _p(drawn, C.c_uint32), _p(passed, C.c_uint32), n))
         return drawn[:n], passed[:n]
+
+    def record_links(self, span: int):
+        """Links between nearby sites (gmx_engine_record_links): count, for every read orientation that maps with exactly one
+        mapping instance, the allele pairs it shows at sites at most ``span`` (1..7; 0: off) site indices apart; see links().
+        Flat PRGs only. Only while nothing is recorded: after creation or reset(). The recording survives reset()."""
+        check(self.lib.gmx_engine_record_links(self.h, int(span)))
+
+    @property
+    def link_span(self) -> int:
+        """The span of record_links (0: off)."""
+        return int(self.lib.gmx_engine_links(self.h))
+
+    def links(self):
+        """``(off, words)``: the layout (Index.link_layout of the recorded span) and the link block's uint32 counters
+        (gmx_coverage_fetch_links); link_matrix() cuts one matrix out of them."""
+        off = self.index.link_layout(self.link_span)
+        n = int(off[-1])
+        words = np.zeros(max(n, 1), dtype=np.uint32)
+        check(self.lib.gmx_coverage_fetch_links(self.h, _p(words, C.c_uint32), n))
+        return off, words[:n]
 
     def set_max_candidates(self, n: int):
         """A limit on a selection's candidates (gmx_engine_set_max_candidates; 0: none): a task with a variant-site class whose
@@ -1007,6 +1046,18 @@ class QuasimapperGroup:
         view = self._member(member)
         try:
             return view.site_ambiguity()
+        finally:
+            view.h = None
+
+    def record_links(self, span: int):
+        """Links between nearby sites on every member with one span, or on none (gmx_group_record_links; Quasimapper.record_links)."""
+        check(self.lib.gmx_group_record_links(self.h, int(span)))
+
+    def links(self, member: int = 0):
+        """Quasimapper.links of engine `member` (after :meth:`allreduce`: member 0 holds the sums of the whole job)."""
+        view = self._member(member)
+        try:
+            return view.links()
         finally:
             view.h = None
 

@@ -465,6 +465,7 @@ typedef struct gmx_queue_counts {
   uint64_t log_replays;       /* since the engine was created: rounds in which entries that found the grouped log full were redone */
   uint64_t log_replayed_entries; /* ... and how many entries those rounds redid */
   uint64_t overflow_split;    /* overflow tasks whose share of a slot under the 16-lane split search did not suffice: redone by one lane with a whole slot */
+  uint64_t coop_rejected;     /* entries the cooperative coverage kernel left to the serial instances of its three queues */
 } gmx_queue_counts;
 int gmx_engine_queue_counts(gmx_engine *e, gmx_queue_counts *out);
 
@@ -603,6 +604,37 @@ int gmx_coverage_fetch_strand(gmx_engine *e, int strand, uint32_t *allele_sum, u
 int gmx_engine_record_site_ambiguity(gmx_engine *e, int on);
 int gmx_engine_site_ambiguity(gmx_engine *e);
 int gmx_coverage_fetch_site_ambiguity(gmx_engine *e, uint32_t *drawn, uint32_t *passed, uint64_t n_sites);
+/* Links between nearby sites: which alleles were seen on the same read (off by default; nothing changes while it is off; flat PRGs
+ * only). A'(s) is site s's allele count if it is at most 8, else 0 (and 0 past the last site); a site with A'(s) > 0 is LINKABLE.
+ * With span D in 1..7 the engine keeps, for every linkable site s and every d in 1..D with A'(s + d) > 0, a matrix M(s, d) of
+ * A'(s) x A'(s + d) uint32 counters, row-major [allele at s][allele at s + d]; alleles are 0-based in the order of
+ * allele_sum_coverage's columns, sites are the engine's site indices (marker - 5) >> 1.
+ *   A task (read, orientation) takes part when it is exactly mapped with exactly ONE mapping instance (n == 1 of its position
+ *   record): ambiguous reads phase nothing, and the counts depend neither on the seeds nor on rng_mode. With its loci
+ *   (s_1, a_1) < ... < (s_m, a_m) — its path, and in front of it the allele it starts inside, if any — it adds 1 to
+ *   M(s_i, s_j - s_i)[a_i][a_j] for every i < j with s_j - s_i <= D and both sites linkable. A pair with a non-linkable end is
+ *   skipped, the task's other pairs count. Strands are not split. A task counts exactly once, whichever tier, replay or workspace
+ *   finishes it.
+ * Layout of the block (a function of the index and the span alone): off[0] = 0, off[s + 1] - off[s] = A'(s) * sum_{d=1..D} A'(s + d);
+ * M(s, d) starts at off[s] + A'(s) * sum_{e=1..d-1} A'(s + e).
+ *   gmx_index_link_layout     off[0 .. n_sites] for a span (pure host; n_sites_plus_1 = the index's sites + 1); GMX_EINVAL on a
+ *     nested index or a span outside 0..7.
+ *   gmx_engine_record_links   span 0 (off) to 7; the rule of gmx_engine_record_strands: only while nothing is recorded (GMX_EINVAL
+ *     otherwise), the old state stays when an allocation fails, a reset zeroes the counts and keeps the span. GMX_EINVAL on a nested
+ *     index, a span outside 0..7, or a block beyond 2^32 words. Combines with gmx_engine_record_strands and
+ *     gmx_engine_record_site_ambiguity.
+ *   gmx_engine_links          the span (0: off).
+ *   gmx_coverage_fetch_links  the off[n_sites] words once everything handed over has been recorded; GMX_EINVAL with recording off or
+ *     an n_words that is not off[n_sites].
+ *   gmx_coverage_device       with recording on `fused` is [block(s) | site ambiguity | off[n_sites] words rounded up to 64 | 32 limb
+ *     words]: the exchange sums the links with the coverage. Every engine of one exchange records the same span:
+ *     gmx_group_record_links sets all members of a group or none (gmx_group_allreduce returns GMX_EINVAL when the spans differ);
+ *     under gmx_comm_* every rank calls gmx_engine_record_links with the same span before it maps (nothing can check that across
+ *     processes). */
+int gmx_index_link_layout(const gmx_index *ix, int span, uint64_t *off, uint64_t n_sites_plus_1);
+int gmx_engine_record_links(gmx_engine *e, int span);
+int gmx_engine_links(gmx_engine *e);
+int gmx_coverage_fetch_links(gmx_engine *e, uint32_t *words, uint64_t n_words);
 /* Grouped counts of sites with more than 8 alleles (grouped_allele_counts.cpp:17-49 for sites without dense slots).
  * Returns the number of uint32 words of the log (and copies it when it fits cap_words). The log is a sequence of records
  *   [site_index, n_ids, ids...]                                     worth +1, or
@@ -748,6 +780,10 @@ int gmx_group_record_strands(gmx_group *g, int on);
 /* The per-site ambiguity counts on every member (gmx_engine_record_site_ambiguity; the same rule). All members or none. After
  * gmx_group_allreduce, gmx_coverage_fetch_site_ambiguity on any member returns the group's sums, as gmx_coverage_fetch does. */
 int gmx_group_record_site_ambiguity(gmx_group *g, int on);
+/* The links between nearby sites on every member, with one span (gmx_engine_record_links; the same rule). All members or none: when
+ * one refuses, those before it go back to the span they had. After gmx_group_allreduce, gmx_coverage_fetch_links on member 0
+ * returns the group's sums. */
+int gmx_group_record_links(gmx_group *g, int span);
 /* The limit on candidates on every member (gmx_engine_set_max_candidates; the same rule). All members or none: when one refuses,
  * those before it go back to the limit they had. */
 int gmx_group_set_max_candidates(gmx_group *g, uint32_t limit);
