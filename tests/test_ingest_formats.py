@@ -8,8 +8,9 @@ import json
 import numpy as np
 import pytest
 
+from bam_common import bam_bytes, header_length, record, reverse_complement
 from ingest_formats_common import cli_reads, fasta_text, generated_files, gram, parse, parse_check_lines
-from test_ingest import bgzf, check_reads
+from test_ingest import bgzf, check_reads, expected_planes
 
 pytestmark = pytest.mark.gpu
 
@@ -92,6 +93,76 @@ def test_a_header_line_in_a_lines_file_and_sequence_before_a_fasta_header_are_de
     ing.reset()
     ing.submit_text(0, b"\nACGT\n>x\nACGT\n", True)
     assert ing.wait(0).status == GMX_INGEST_BAD_RECORD
+    ing.close()
+
+
+def _one_list_of_reads(variant):
+    """Lengths at the edges of a plane word (32 bases) and, ragged, of the offsets form: the reads follow each other at every kind
+    of offset modulo 32, so (off + len) >> 5 crosses no word, one and several."""
+    rng = np.random.default_rng(11)
+    seq = lambda n: "".join("ACGT"[c] for c in rng.integers(0, 4, n))  # noqa: E731
+    if variant == "uniform":
+        return [seq(33) for _ in range(40)]
+    lens = [1, 2, 31, 32, 33, 63, 64, 65, 95, 96, 97, 7, 8, 16, 45, 50]
+    seqs = [seq(n) for n in lens + lens[::-1] + [64, 32, 32, 1, 31, 97, 2, 96]]
+    if variant == "unencodable":  # an unencodable base at positions 0, 31, 32 and len - 1, in reads next to clean ones
+        for r, at in ((0, 0), (3, 31), (4, 32), (6, 31), (7, 32), (9, 0), (10, 96), (12, 7), (14, 31), (21, 32), (25, 63)):
+            assert at < len(seqs[r])
+            seqs[r] = seqs[r][:at] + "N" + seqs[r][at + 1:]
+    return seqs
+
+
+def _five_ways(seqs):
+    """(name, format, text, BAM header bytes) of the same reads; the BAM stores every second read on the reverse strand."""
+    from gramtools_amd import GMX_INGEST_FORMAT_BAM, GMX_INGEST_FORMAT_FASTA, GMX_INGEST_FORMAT_FASTQ, GMX_INGEST_FORMAT_LINES
+    bam = bam_bytes([record(reverse_complement(s) if i % 2 else s, flag=0x10 if i % 2 else 0, name=f"r{i}") for i, s in enumerate(seqs)], [("chr1", 1000)])
+    return [("fastq", GMX_INGEST_FORMAT_FASTQ, "".join(f"@r{i}\n{s}\n+\n{'I' * len(s)}\n" for i, s in enumerate(seqs)).encode(), 0),
+            ("fasta-wrap7", GMX_INGEST_FORMAT_FASTA, fasta_text(seqs, 7), 0),
+            ("fasta", GMX_INGEST_FORMAT_FASTA, fasta_text(seqs), 0),
+            ("lines", GMX_INGEST_FORMAT_LINES, "".join(s + "\n" for s in seqs).encode(), 0),
+            ("bam", GMX_INGEST_FORMAT_BAM, bam, header_length(bam))]
+
+
+@pytest.mark.parametrize("variant", ["ragged", "uniform", "unencodable"])
+def test_the_same_reads_in_every_format_give_the_same_planes(variant):
+    """One list of reads as four-line FASTQ, FASTA wrapped at 7 (the gather across lines), FASTA unwrapped, one read per line and
+    BAM with every second record on the reverse strand (odd and even mirrored window starts), each in one chunk: the pack kernels
+    place a read's words by one rule (ing_pack_words; gmx_bam_pack_kernel has it written out), so planes, offsets and skip flags
+    are bit-identical across the formats and equal the host packer's. With unencodable bases ('N'; BAM code 15) the skip flags agree, any_skip is set and the other reads' planes
+    are untouched (a flagged read's own planes are whatever its letters' bits give: they are not compared)."""
+    from gramtools_amd import Ingest
+    seqs = _one_list_of_reads(variant)
+    exp, offs, uniform = expected_planes(seqs)
+    assert uniform == (33 if variant == "uniform" else 0)
+    skip_exp = np.array([0 if set(s) <= set("ACGT") else 1 for s in seqs], dtype=np.uint8)
+    assert bool(skip_exp.any()) == (variant == "unencodable")
+    keep = np.ones(int(exp.planes.size), dtype=bool)  # the pairs of the reads without an unencodable base, and the ragged form's spare ones
+    for r in np.flatnonzero(skip_exp):
+        p0 = (int(offs[r]) >> 5) + int(r)
+        keep[p0:p0 + (len(seqs[r]) + 31) // 32] = False
+    ing = Ingest(max_text_bytes=1 << 16)
+    first = None
+    for name, fmt, text, header in _five_ways(seqs):
+        ing.set_format(fmt)
+        ing.reset()
+        if header:
+            ing.set_bam_header(header)
+        ing.submit_text(0, text, True)
+        res = ing.wait(0)
+        assert (res.status, res.n_reads, res.uniform_len, res.n_bases) == (0, len(seqs), uniform, int(offs[-1])), name
+        assert bool(res.any_skip) == bool(skip_exp.any()), name
+        n_pairs = int(res.n_pairs)
+        assert n_pairs == (len(seqs) * 2 if uniform else (int(offs[-1]) >> 5) + len(seqs)), name
+        got = ing.fetch_reads(0, res)
+        planes = np.where(keep[:n_pairs], got.planes[:n_pairs], 0)
+        assert (planes == np.where(keep[:n_pairs], exp.planes[:n_pairs], 0)).all(), name  # (b) the host packer's
+        assert (got.skip[:len(seqs)] == skip_exp).all(), name
+        assert uniform or (got.offsets == offs).all(), name
+        if first is None:
+            first = (planes, got.skip.copy(), got.offsets)
+        else:  # (a) bit-identical across the formats
+            assert (planes == first[0]).all() and (got.skip == first[1]).all(), name
+            assert uniform or (got.offsets == first[2]).all(), name
     ing.close()
 
 
