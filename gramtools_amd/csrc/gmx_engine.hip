@@ -70,7 +70,13 @@
 #define GMX_STATUS_MISSING_KMER 5u  // refinement of GMX_TASK_UNMAPPED by the k-mer filter
 #define GMX_STATUS_IGNORED 7u       // reverse-complement task of a forward_only engine: not mapped, not counted
 
-// The rest of this translation unit, in three parts (one TU: the kernels share the contexts, the launch code names the kernels):
+// The rest of this translation unit, in parts (one TU: the kernels share the contexts, the launch code names the kernels):
 #include "gmx_engine_search.h"         // contexts, dfs_run_wave, search kernels, k-mer filter
 #include "gmx_engine_cover_kernels.h"  // coverage kernels, pack kernel
-#include "gmx_engine_host.h"           // engine object, launches, feeds, C ABI
+// the host side and the device half of the C ABI, in this order:
+#include "gmx_engine_state.h"          // engine object: device buffers, batch workspace, per-read logs, feed slots; waits, queued reset
+#include "gmx_engine_create.h"         // default options, the shared device index, creation, destruction, the resets
+#include "gmx_engine_batch.h"          // workspace growth, one batch's launches on three streams, the grouped log's drain / settle / replay
+#include "gmx_engine_feeds.h"          // gmx_map_reads_*: the slot ring of the host feeds, the reserve calls, page-locked host memory
+#include "gmx_engine_readback.h"       // sync, timing, queue counts, coverage read-back, block-layout switches, read logs, log import / export
+#include "gmx_engine_debug.h"          // test hooks (final SearchStates of a task, the search loop on given states, owned device bytes)

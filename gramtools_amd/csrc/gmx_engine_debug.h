@@ -172,7 +172,7 @@ int debug_put_state(gmx_engine *e, DebugWriter &w, const GmxFinalState &st, Node
 }
 
 int debug_pools(gmx_engine *e, GmxDebugPools &p, uint32_t n_in_words, uint32_t n_pairs) {
-  const uint32_t S = std::max<uint32_t>(e->big.max_states, 64u), N = std::max<uint32_t>(e->big.max_path_nodes, 64u);
+  const uint32_t S = std::max<uint32_t>(e->ws.big.max_states, 64u), N = std::max<uint32_t>(e->ws.big.max_path_nodes, 64u);
   int rc;
   if ((rc = e->alloc(&p.states, S, false))) return rc;
   if ((rc = e->alloc(&p.stack, (size_t)S * GMX_STACK_WORDS, false))) return rc;
@@ -206,6 +206,13 @@ int gmx_engine_debug_keep_states(gmx_engine *e, int on) try {
   return GMX_OK;
 } GMX_GUARD_INT("gmx_engine_debug_keep_states")
 
+uint64_t gmx_engine_debug_owned_bytes(gmx_engine *e) try {
+  uint64_t n = 0;
+  for (const gmx_engine *w : {(const gmx_engine *)e, e ? (const gmx_engine *)e->twin : nullptr})
+    if (w) n += w->allocs.bytes() + w->ws.allocs.bytes();
+  return n;
+} GMX_GUARD_ZERO("gmx_engine_debug_owned_bytes")
+
 int gmx_debug_final_states(gmx_engine *e, uint64_t task, uint32_t *out, uint64_t cap_words, uint64_t *n_words, int *tier) try {
   if (!e || !n_words) {
     gmx_set_error("gmx_debug_final_states: null argument");
@@ -227,7 +234,7 @@ int gmx_debug_final_states(gmx_engine *e, uint64_t task, uint32_t *out, uint64_t
   {
     const uint32_t n_huge = c(11);
     std::vector<uint32_t> huge(n_huge);
-    if (n_huge) HIP_TRY(hipMemcpy(huge.data(), e->d_huge, n_huge * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (n_huge) HIP_TRY(hipMemcpy(huge.data(), e->ws.o.huge_list, n_huge * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (uint32_t t : huge)
       if (t == task) {
         gmx_set_error("gmx_debug_final_states: the task was searched by the last tier, which keeps no states");
@@ -237,12 +244,12 @@ int gmx_debug_final_states(gmx_engine *e, uint64_t task, uint32_t *out, uint64_t
   // large-capacity slots: instance 0 of the split search / the probe kernel's queue [0, c1), the extend kernel's queue
   // [c1, c1 + c9), the one-lane search of what the split search left [c1 + c9, c1 + c9 + c29). A task redone by a later
   // tier owns a later slot, and the slots of its failed attempts say "no state": the last slot with states counts.
-  const uint32_t used = (uint32_t)std::min<uint64_t>((uint64_t)c(1) + c(9) + c(29), e->big.max_slots);
+  const uint32_t used = (uint32_t)std::min<uint64_t>((uint64_t)c(1) + c(9) + c(29), e->ws.big.max_slots);
   if (used) {
     std::vector<uint32_t> owner(used), nf(used), over(std::min<uint32_t>(c(1), used));
-    HIP_TRY(hipMemcpy(owner.data(), e->big.task_of_slot, used * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(nf.data(), e->big.n_final, used * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (!over.empty()) HIP_TRY(hipMemcpy(over.data(), e->d_overflow, over.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(owner.data(), e->ws.big.task_of_slot, used * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(nf.data(), e->ws.big.n_final, used * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (!over.empty()) HIP_TRY(hipMemcpy(over.data(), e->ws.o.overflow_list, over.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     // which of the first c(1) slots were really written this batch: the queue entry names the task
     bool in_slots = false;
     for (uint32_t s = used; s-- > 0;) {
@@ -257,11 +264,11 @@ int gmx_debug_final_states(gmx_engine *e, uint64_t task, uint32_t *out, uint64_t
       std::vector<GmxFinalState> st(n);
       if (inst) {
         uint32_t first = 0, width = 0;
-        HIP_TRY(hipMemcpy(&first, e->d_inst_first + s, 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(&width, e->d_inst_width + s, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&first, e->ws.o.inst_first + s, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&width, e->ws.o.inst_remaining_width + s, 4, hipMemcpyDeviceToHost));
         if (n > width * GMX_INST_STATES) continue;  // its instances ran out of their pools: redone elsewhere
-        HIP_TRY(hipMemcpy(st.data(), e->d_inst_states + (size_t)first * GMX_INST_STATES, n * sizeof(GmxFinalState), hipMemcpyDeviceToHost));
-        const GmxPathNode *arena = e->d_inst_arena + (size_t)first * GMX_FAST_ARENA;
+        HIP_TRY(hipMemcpy(st.data(), e->ws.o.inst_states + (size_t)first * GMX_INST_STATES, n * sizeof(GmxFinalState), hipMemcpyDeviceToHost));
+        const GmxPathNode *arena = e->ws.o.inst_arena + (size_t)first * GMX_FAST_ARENA;
         w.put(n);
         for (uint32_t i = 0; i < n; ++i) {
           rc = debug_put_state(e, w, st[i], [&](uint32_t h, GmxPathNode &nd) {
@@ -272,9 +279,9 @@ int gmx_debug_final_states(gmx_engine *e, uint64_t task, uint32_t *out, uint64_t
         }
         if (tier) *tier = 2;
       } else {
-        if (n > e->big.max_states) continue;
-        HIP_TRY(hipMemcpy(st.data(), e->big.states + (size_t)s * e->big.max_states, n * sizeof(GmxFinalState), hipMemcpyDeviceToHost));
-        const GmxPathNode *arena = e->big.arena + (size_t)s * e->big.max_path_nodes;
+        if (n > e->ws.big.max_states) continue;
+        HIP_TRY(hipMemcpy(st.data(), e->ws.big.states + (size_t)s * e->ws.big.max_states, n * sizeof(GmxFinalState), hipMemcpyDeviceToHost));
+        const GmxPathNode *arena = e->ws.big.arena + (size_t)s * e->ws.big.max_path_nodes;
         w.put(n);
         for (uint32_t i = 0; i < n; ++i) {
           rc = debug_put_state(e, w, st[i], [&](uint32_t h, GmxPathNode &nd) {
@@ -297,11 +304,11 @@ int gmx_debug_final_states(gmx_engine *e, uint64_t task, uint32_t *out, uint64_t
   }
   // the fast tier: finals[task * GMX_FAST_STATES ..], node k of the task at arena[k * stride + task]
   uint32_t packed = 0;
-  HIP_TRY(hipMemcpy(&packed, e->d_n_final + task, 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&packed, e->ws.o.n_final + task, 4, hipMemcpyDeviceToHost));
   const uint32_t n = std::min<uint32_t>(packed & 0xFFu, GMX_FAST_STATES);
   std::vector<GmxFinalState> st(n);
-  if (n) HIP_TRY(hipMemcpy(st.data(), e->d_finals + (size_t)task * GMX_FAST_STATES, n * sizeof(GmxFinalState), hipMemcpyDeviceToHost));
-  const GmxPathNode *arena = e->d_arena + task;
+  if (n) HIP_TRY(hipMemcpy(st.data(), e->ws.o.finals + (size_t)task * GMX_FAST_STATES, n * sizeof(GmxFinalState), hipMemcpyDeviceToHost));
+  const GmxPathNode *arena = e->ws.o.arena + task;
   w.put(n);
   for (uint32_t i = 0; i < n; ++i) {
     rc = debug_put_state(e, w, st[i], [&](uint32_t h, GmxPathNode &nd) {

@@ -716,6 +716,10 @@ class Quasimapper:
         """From the next batch on every task's final states stay readable (debug_final_states)."""
         check(self.lib.gmx_engine_debug_keep_states(self.h, 1 if on else 0))
 
+    def debug_owned_bytes(self):
+        """Device bytes this engine owns: workspace, staging, slots, accumulators (not the shared index, not the per-read logs)."""
+        return int(self.lib.gmx_engine_debug_owned_bytes(self.h))
+
     def debug_final_states(self, read, orientation=0):
         """Final SearchStates of (read, orientation) of the last launch, as search_read_backwards leaves them. -> (states, tier)"""
         n, tier = C.c_uint64(0), C.c_int(-1)

@@ -432,6 +432,11 @@ int gmx_index_check_stock_files(const gmx_index *ix, const char *gram_dir, gmx_s
  *   given states: position by position; out = the states that stay mapping instances of a site, nonvariant_sa =
  *   the SA indices of the path-less positions outside every site (the reference keeps them as path-less states). */
 int gmx_engine_debug_keep_states(gmx_engine *e, int on);
+/* Device bytes this engine owns now: its batch workspace, the bit planes and staging buffers of the host feeds, their upload
+ * slots, the accumulator block and the other buffers made with the engine, and the same of its second workspace if it has one.
+ * Not counted: the index tables shared by the engines of a device, the per-read logs. A superseded upload-slot buffer has been
+ * freed; a superseded workspace, bit-plane or staging buffer stays (and counts) until the engine is destroyed. */
+uint64_t gmx_engine_debug_owned_bytes(gmx_engine *e);
 /* Allocation-failure injection (tests/test_alloc_failure.py): the nth call of operator new made by libgmx.so's own code
  * from now on throws std::bad_alloc, once; nth < 0: only count allocations; nth == 0: off, counting stops (the counter is one
  * cache line every allocating thread hits: it is on only between such calls); also GMX_TEST_FAIL_ALLOC=n in the environment
