@@ -305,6 +305,17 @@ int gmx_debug_final_states(gmx_engine *e, uint64_t task, uint32_t *out, uint64_t
   // the fast tier: finals[task * GMX_FAST_STATES ..], node k of the task at arena[k * stride + task]
   uint32_t packed = 0;
   HIP_TRY(hipMemcpy(&packed, e->ws.o.n_final + task, 4, hipMemcpyDeviceToHost));
+  // A task the probe kernel parked and the extend kernel then found dead keeps the count of its PARKED entries (nobody reads
+  // the count of a dead task, so no kernel clears it): the extend kernel's dead queue says "no state".
+  // (This engine's own workspace, like everything above: with keep_states every launch goes to the engine itself, never to its
+  // twin — pick_target. The queue is copied per call: a test hook, a few hundred tasks.)
+  if (packed & 0xFFu) {
+    const uint32_t n_dead2 = std::min(c(12), e->ws.o.list_stride);
+    std::vector<uint32_t> dead2(n_dead2);
+    if (n_dead2)
+      HIP_TRY(hipMemcpy(dead2.data(), e->ws.o.task_lists + (size_t)GMX_TL_DEAD2 * e->ws.o.list_stride, n_dead2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (std::find(dead2.begin(), dead2.end(), (uint32_t)task) != dead2.end()) packed = 0;
+  }
   const uint32_t n = std::min<uint32_t>(packed & 0xFFu, GMX_FAST_STATES);
   std::vector<GmxFinalState> st(n);
   if (n) HIP_TRY(hipMemcpy(st.data(), e->ws.o.finals + (size_t)task * GMX_FAST_STATES, n * sizeof(GmxFinalState), hipMemcpyDeviceToHost));

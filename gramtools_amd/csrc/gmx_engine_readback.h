@@ -139,6 +139,16 @@ int gmx_engine_queue_counts(gmx_engine *e, gmx_queue_counts *out) try {
   return GMX_OK;
 } GMX_GUARD_INT("gmx_engine_queue_counts")
 
+int gmx_debug_straggler_counts(gmx_engine *e, uint64_t out[3]) try {
+  HIP_TRY(hipSetDevice(e->opts.device));
+  HIP_TRY(hipDeviceSynchronize());
+  static_assert(GMX_EXTRA_PASSES == 3, "gmx_debug_straggler_counts: one count per straggler list");
+  uint32_t raw[GMX_N_COUNTERS * GMX_CNT_STRIDE];
+  HIP_TRY(hipMemcpy(raw, (e->twin && e->last_on_twin ? e->twin : e)->d_counters, sizeof(raw), hipMemcpyDeviceToHost));  // (the workspace of the LAST launch)
+  for (uint32_t pass = 0; pass < GMX_EXTRA_PASSES; ++pass) out[pass] = raw[(GMX_CNT_ALIVE2 + pass) * GMX_CNT_STRIDE];
+  return GMX_OK;
+} GMX_GUARD_INT("gmx_debug_straggler_counts")
+
 int gmx_coverage_device(gmx_engine *e, gmx_device_coverage *out) try {
   {
     int frc = flush_reset(e);

@@ -688,6 +688,12 @@ class Quasimapper:
         check(self.lib.gmx_engine_queue_counts(self.h, C.byref(q)))
         return {n: int(getattr(q, n)) for n, _ in q._fields_}
 
+    def debug_straggler_counts(self):
+        """Tasks of the last batch the extend kernel parked for its straggler passes 0, 1 and 2 (gmx_debug_straggler_counts)."""
+        out = (C.c_uint64 * 3)()
+        check(self.lib.gmx_debug_straggler_counts(self.h, out))
+        return [int(x) for x in out]
+
     # ---- test hooks: SearchStates of the HIP path (gmx.h; states as (lo, hi, [(site, allele)...], [(site, -1)...])) ----
     @staticmethod
     def _states_to_words(states):

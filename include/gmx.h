@@ -473,6 +473,9 @@ typedef struct gmx_queue_counts {
   uint64_t coop_rejected;     /* entries the cooperative coverage kernel left to the serial instances of its three queues */
 } gmx_queue_counts;
 int gmx_engine_queue_counts(gmx_engine *e, gmx_queue_counts *out);
+/* Test hook beside it: out[pass] = the tasks of the LAST batch that the extend kernel parked with work left when its iteration
+ * budget ran out (GMX_EXTEND_BUDGET, GMX_EXTEND_PASSES), for its straggler pass 0, 1 and 2. All zero without a budget. */
+int gmx_debug_straggler_counts(gmx_engine *e, uint64_t out[3]);
 
 /* The i-th master-generator draws for reads_per_file (quasimap.cpp:120-141: 5000 draws per batch of
  * <= 5000 reads, one mt19937(master_seed) shared by all files). `out` receives sum(reads_per_file) seeds. */

@@ -14,26 +14,9 @@ from golden_runner import BASES, load_cases, prg_ints, seq, st
 from gramtools_amd import Index, Quasimapper
 from gramtools_amd.synth import bracket_to_ints, nested_prg, simulate_graph_reads
 from oracle import Oracle
+from states_common import encapsulated_instances, instances
 
 pytestmark = pytest.mark.gpu
-
-
-def instances(states):
-    out = []
-    for s in states:
-        lo, hi = int(s[0]), int(s[1])
-        tvd = tuple((int(m), int(a)) for m, a in (s[2] if len(s) > 2 else []))
-        tvg = tuple(int(x[0]) for x in (s[3] if len(s) > 3 else []))
-        out += [(i, tvd, tvg) for i in range(lo, hi + 1)]
-    return sorted(out)
-
-
-def encapsulated_instances(qm, states):
-    """the device's handle_allele_encapsulated_states on `states`, as instances"""
-    if not states:
-        return []
-    inside, outside = qm.debug_encapsulate(states)
-    return sorted(instances(inside) + [(i, (), ()) for i in outside])
 
 
 STATE_OPS = {"search_read_backwards", "search_base_backwards", "process_read_char", "process_read_char_from_kmer", "expect_kmer",
