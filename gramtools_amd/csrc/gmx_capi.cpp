@@ -466,6 +466,31 @@ int gmx_debug_suffix_array_u16(const uint16_t *text, uint64_t n, uint16_t *out) 
   }
 } GMX_GUARD_INT("gmx_debug_suffix_array_u16")
 
+int gmx_debug_suffix_array_u32(const uint32_t *text, uint64_t n, int threads, uint32_t *out) try {
+  if (!text || !out || n == 0) {
+    gmx_set_error("gmx_debug_suffix_array_u32: a text of at least one symbol and an output array");
+    return GMX_EINVAL;
+  }
+  std::vector<uint32_t> t(text, text + n), sa;
+  gmx::build_suffix_array(t, sa, threads);  // (a builder error leaves through the guard: GMX_EINVAL with its message)
+  memcpy(out, sa.data(), sa.size() * sizeof(uint32_t));
+  return GMX_OK;
+} GMX_GUARD_INT("gmx_debug_suffix_array_u32")
+
+int gmx_debug_suffix_presort(const uint32_t *text, uint64_t n, uint32_t *sa, uint32_t *mask_words) try {
+  if (!text || !sa || !mask_words || n == 0 || n >= 0xFFFFFFFEull) {
+    gmx_set_error("gmx_debug_suffix_presort: a text of 1 to 2^32 - 3 symbols and both output arrays");
+    return GMX_EINVAL;
+  }
+  std::vector<uint32_t> mask;
+  if (!gmx::g_device_suffix_presort || !gmx::g_device_suffix_presort(text, (size_t)n, sa, mask)) {
+    gmx_set_error("gmx_debug_suffix_presort: no device suffix pre-sort (no usable device, or a host-only build)");
+    return GMX_ENODEV;
+  }
+  memcpy(mask_words, mask.data(), ((size_t)(n + 31) / 32) * sizeof(uint32_t));
+  return GMX_OK;
+} GMX_GUARD_INT("gmx_debug_suffix_presort")
+
 int gmx_index_copy_sa(const gmx_index *ix, uint32_t *out) try {
   memcpy(out, ix->h.sa.data(), ix->h.sa.size() * 4);
   return GMX_OK;

@@ -168,8 +168,15 @@ void sort_pairs(Scratch &sc, const K *keys_in, K *keys_out, const V *vals_in, V 
 }
 
 // hipCUB's scans count their items in an int: pieces of 2^30 with the running value carried over
+// (GMX_SORT_SCAN_PIECE: a shorter piece, in items — the tests run the carry on small texts; read on every call)
+size_t scan_piece() {
+  const size_t full = (size_t)1 << 30;
+  const char *s = getenv("GMX_SORT_SCAN_PIECE");
+  const unsigned long long v = s ? strtoull(s, nullptr, 10) : 0ull;
+  return v == 0 || v > full ? full : (size_t)v;
+}
 void exclusive_sum(Scratch &sc, const uint32_t *in, uint32_t *out, size_t n) {
-  const size_t piece = (size_t)1 << 30;
+  const size_t piece = scan_piece();
   uint32_t carry = 0;
   for (size_t off = 0; off < n; off += piece) {
     const int len = (int)std::min(piece, n - off);
@@ -185,7 +192,7 @@ void exclusive_sum(Scratch &sc, const uint32_t *in, uint32_t *out, size_t n) {
   }
 }
 void running_max_in_place(Scratch &sc, uint32_t *v, size_t n) {
-  const size_t piece = (size_t)1 << 30;
+  const size_t piece = scan_piece();
   uint32_t carry = 0;
   for (size_t off = 0; off < n; off += piece) {
     const int len = (int)std::min(piece, n - off);

@@ -102,6 +102,15 @@ int gmx_index_bubble_order(const gmx_index *ix, uint32_t *site_markers_out);
  * longer than 2^15 drive it with the index type's top bit in use, as whole-human PRGs (> 2^31 symbols) drive the
  * 32-bit instance the index uses (SA_Index is uint32_t in the reference, search/types.hpp:19). */
 int gmx_debug_suffix_array_u16(const uint16_t *text, uint64_t n, uint16_t *out);
+/* The index builder's suffix array of a raw text (n symbols, ending with the only 0; out: n entries), by the route a real
+ * build takes: GMX_SAIS, GMX_PSORT_MIN, GMX_DEVICE_BUILD, GMX_NO_DEVICE_SORT and GMX_DEVICE_SORT_MAY_FALL_BACK are read as
+ * there. threads <= 0: all hardware threads. A builder error is GMX_EINVAL with its message. */
+int gmx_debug_suffix_array_u32(const uint32_t *text, uint64_t n, int threads, uint32_t *out);
+/* What the device pre-sort (gmx_suffixsort.hip) hands to the host, before any repair: sa (n entries) ordered by the two
+ * 12-symbol keys, and bit p of mask_words ((n + 31) / 32 words) set when sa[p] still ties with sa[p - 1]. The keys
+ * hold symbols below 2^28 (the builder sorts other texts on the host). GMX_ENODEV without a device or in a build without
+ * the pre-sort. */
+int gmx_debug_suffix_presort(const uint32_t *text, uint64_t n, uint32_t *sa, uint32_t *mask_words);
 int gmx_index_copy_sa(const gmx_index *ix, uint32_t *out);             /* n_text entries (fm_index[i]) */
 int gmx_index_copy_bwt(const gmx_index *ix, uint32_t *out);            /* n_text entries */
 uint32_t gmx_index_rank(const gmx_index *ix, uint32_t upper, uint32_t base); /* dna_bwt_rank, BWT_search.cpp:8-22 */
