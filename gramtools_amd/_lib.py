@@ -145,6 +145,7 @@ SYMBOLS = {
     "gmx_engine_timing": (C.c_int, [_vp, C.POINTER(Timing)]),
     "gmx_engine_queue_counts": (C.c_int, [_vp, C.POINTER(QueueCounts)]),
     "gmx_debug_straggler_counts": (C.c_int, [_vp, _u64p]),
+    "gmx_debug_cover_counts": (C.c_int, [_vp, _u64p]),
     "gmx_stock_read_int_vector": (_i64, [C.c_char_p, _u32, _u64p, _u64, C.POINTER(C.c_uint32)]),
     "gmx_stock_write_int_vector": (C.c_int, [C.c_char_p, _u64p, _u64, _u32, C.c_int]),
     "gmx_index_write_stock_files": (C.c_int, [_vp, C.c_char_p]),

@@ -140,6 +140,24 @@ struct GmxScratchFixed {  // the fixed tiers: Env::I_MAX .. are compile-time con
   static constexpr uint32_t total = Env::I_MAX * (GmxScratch<Env>::ITEM_W + 1) + Env::I_MAX * (1 + Env::B_MAX) + Env::LOC_MAX * 2 + Env::H_MAX * 3 + 2 * GmxPathMax<Env>::value + 1;
 };
 
+// The capacities of the coverage ladder's fixed tiers, stated once: the engine's instances (gmx_engine_cover_kernels.h) and
+// the host emulation's mirrors (tests/hostemu/hostemu.cpp) are built from these. A tier holds `items` items, `key_sites`
+// level-0 sites per item key, `loci` (site, allele) pairs, `hull` per-base entries and `path` cached traversed sites; a task
+// with one more of any of the first four has recorded nothing and goes to the next tier.
+struct GmxTierCaps {
+  uint32_t items, key_sites, loci, hull, path;
+};
+constexpr GmxTierCaps GMX_CAPS_LDS{4, 12, 24, 24, GMX_PATH_CACHE};          // CoverEnvLds: first one-lane tier of the fast pass's tasks
+constexpr GmxTierCaps GMX_CAPS_MID{12, 12, 48, 48, GMX_PATH_CACHE};         // CoverEnvMid: large-capacity and instance-searched tasks
+constexpr GmxTierCaps GMX_CAPS_REGULAR{24, 16, 64, 64, GMX_PATH_CACHE};     // CoverEnv: second one-lane tier of the fast pass's tasks
+constexpr GmxTierCaps GMX_CAPS_BIG{1024, 32, 1024, 1024, GMX_PATH_CACHE};   // CoverEnvBig: global memory; beyond it the heap-backed tier
+constexpr GmxTierCaps GMX_CAPS_COOP_ITEM{1, 16, 24, 1, 24};                 // CoopSizes<3|2>::Item: one lane's item
+constexpr GmxTierCaps GMX_CAPS_COOP_CLASS{1, 1, 48, 48, 8};                 // CoopSizes<3|2>::Class: the drawn class's union
+constexpr GmxTierCaps GMX_CAPS_COOP5_ITEM{1, 8, 12, 1, GMX_PATH_CACHE};     // CoopSizes<5>::Item
+constexpr GmxTierCaps GMX_CAPS_COOP5_CLASS{1, 1, 24, 24, GMX_PATH_CACHE};   // CoopSizes<5>::Class
+constexpr uint32_t GMX_COOP_UNITS = 16;  // lanes per task of the cooperative instances: a task with more units is left to the one-lane ones
+#define GMX_TIER_ARGS(c) (c).items, (c).key_sites, (c).loci, (c).hull, (c).path
+
 GMX_HD bool gmx_in_bubble(const GmxNode &n) { return n.allele != -1 && n.site != 0; }
 // A final state is an SA interval [lo, hi], or — text form (gmx_types.h, GmxTextRec) — the single PRG position lo.
 GMX_HD bool gmx_text_form(uint32_t hi) { return hi == GMX_TEXT_MARK; }

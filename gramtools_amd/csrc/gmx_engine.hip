@@ -63,6 +63,7 @@
 #define GMX_EXTRA_PASSES 3          // (counters 35, 36, 37; task lists GMX_TL_ALIVE2 ..)
 #define GMX_CNT_SINGLE_REST 38u     // compact records gmx_cover_jump_kernel left to gmx_cover_single_rest_kernel (single_rest_list)
 #define GMX_CNT_REPLAY_RECS 32u     // replay: number of compact records to redo (gmx_cover_single_replay_kernel)
+#define GMX_CNT_TAIL_RETRY 39u      // work items the last tier's 64-lane round left to lane 0 with the whole heap (gmx_tail_stage; read by gmx_debug_cover_counts only)
 #ifndef GMX_FAST_ARENA
 #define GMX_FAST_ARENA 48     // path arena nodes per task (fast pass): a read through an MSA region of configs[2] needs 25-40
                               // (24 sent 14 k of a million such reads to the large-capacity pass: 5.1 -> 3.1 ms per batch)

@@ -165,10 +165,10 @@ struct CoverEnvDyn : CoverLogPart {
   __device__ __forceinline__ void sset(uint32_t w, uint32_t v) { scratch[w] = v; }
 };
 
-typedef CoverEnvT<4, 12, 24, 24> CoverEnvLds;         // first tier of the general pass: per-lane scratch in the block's LDS
-typedef CoverEnvT<12, 12, 48, 48> CoverEnvMid;         // the large-capacity pass's tasks (a read in a 10-copy repeat has ~11 items)
-typedef CoverEnvT<24, 16, 64, 64> CoverEnv;           // per-lane scratch of the regular pass
-typedef CoverEnvT<1024, 32, 1024, 1024> CoverEnvBig;  // reads with many mapping instances (repeats)
+typedef CoverEnvT<GMX_TIER_ARGS(GMX_CAPS_LDS)> CoverEnvLds;         // first tier of the general pass: per-lane scratch in the block's LDS
+typedef CoverEnvT<GMX_TIER_ARGS(GMX_CAPS_MID)> CoverEnvMid;         // the large-capacity pass's tasks (a read in a 10-copy repeat has ~11 items)
+typedef CoverEnvT<GMX_TIER_ARGS(GMX_CAPS_REGULAR)> CoverEnv;           // per-lane scratch of the regular pass
+typedef CoverEnvT<GMX_TIER_ARGS(GMX_CAPS_BIG)> CoverEnvBig;  // reads with many mapping instances (repeats)
 
 // ---------------------------------------------------------------------------
 // The last tier. Every pool above has a fixed size per task; a task that exceeds one of them — a read with thousands of
@@ -382,6 +382,7 @@ __device__ void gmx_tail_stage(const GmxIndexView &ix, const BatchView &b, const
   __syncthreads();
   __threadfence();
   const uint32_t retries = n_retry;
+  if (threadIdx.x == 0) o.counters[GMX_CNT_TAIL_RETRY * GMX_CNT_STRIDE] = retries;  // (a test hook's figure: gmx_debug_cover_counts)
   for (uint32_t i = 0; i < retries; ++i) {  // lane 0 alone, the whole heap
     uint32_t task = 0;
     const uint32_t st = gmx_tail_item(ix, b, o, g, acc, lane == 0, o.huge_retry[i], n_search, acc.heap, acc.heap_words, true, task, lk);
@@ -590,13 +591,13 @@ __global__ void __launch_bounds__(GMX_ONE_THREADS) gmx_cover_one_kernel(GmxIndex
 // one-lane instances (whose keys were as short: the last, global-memory one then took 9 of the batch's 15 ms).
 template <int LIST>
 struct CoopSizes {  // instances 3 and 2: the regular tasks' general instance, and what the large-capacity search mapped
-  typedef CoverEnvT<1, 16, 24, 1, 24> Item;    // one item: its record, key, loci window (and the copy of its traversed list)
-  typedef CoverEnvT<1, 1, 48, 48, 8> Class;    // the drawn class: union of loci, hull (no keys; the loci come from the members' windows)
+  typedef CoverEnvT<GMX_TIER_ARGS(GMX_CAPS_COOP_ITEM)> Item;    // one item: its record, key, loci window (and the copy of its traversed list)
+  typedef CoverEnvT<GMX_TIER_ARGS(GMX_CAPS_COOP_CLASS)> Class;    // the drawn class: union of loci, hull (no keys; the loci come from the members' windows)
 };
 template <>
 struct CoopSizes<5> {  // instance 5: the instance-searched reads in repeats (many items, short paths)
-  typedef CoverEnvT<1, 8, 12, 1> Item;
-  typedef CoverEnvT<1, 1, 24, 24> Class;
+  typedef CoverEnvT<GMX_TIER_ARGS(GMX_CAPS_COOP5_ITEM)> Item;
+  typedef CoverEnvT<GMX_TIER_ARGS(GMX_CAPS_COOP5_CLASS)> Class;
 };
 template <int LIST>
 constexpr uint32_t gmx_coop_lds_words() {  // + per group: the drawn item's traversed list as path nodes (the walk's handles)

@@ -149,6 +149,18 @@ int gmx_debug_straggler_counts(gmx_engine *e, uint64_t out[3]) try {
   return GMX_OK;
 } GMX_GUARD_INT("gmx_debug_straggler_counts")
 
+// The coverage ladder's queue lengths one by one (gmx_engine_queue_counts sums some of them and leaves others out): only what
+// the kernels of the LAST launch wrote anyway. The order is that of gmx.h.
+int gmx_debug_cover_counts(gmx_engine *e, uint64_t out[12]) try {
+  HIP_TRY(hipSetDevice(e->opts.device));
+  HIP_TRY(hipDeviceSynchronize());
+  uint32_t raw[GMX_N_COUNTERS * GMX_CNT_STRIDE];
+  HIP_TRY(hipMemcpy(raw, (e->twin && e->last_on_twin ? e->twin : e)->d_counters, sizeof(raw), hipMemcpyDeviceToHost));  // (the workspace of the LAST launch)
+  static const uint32_t which[12] = {8u, GMX_CNT_GENERAL_REST, 27u, 26u, 28u, 13u, 4u, 15u, 11u, 7u, 25u, GMX_CNT_TAIL_RETRY};
+  for (int i = 0; i < 12; ++i) out[i] = raw[which[i] * GMX_CNT_STRIDE];
+  return GMX_OK;
+} GMX_GUARD_INT("gmx_debug_cover_counts")
+
 int gmx_coverage_device(gmx_engine *e, gmx_device_coverage *out) try {
   {
     int frc = flush_reset(e);

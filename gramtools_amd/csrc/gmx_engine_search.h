@@ -685,7 +685,9 @@ template <class Ctx, class Push>
 __device__ void load_seed(const GmxIndexView &ix, const GmxSeed *table, uint32_t code, Ctx &ctx, Push push) {
   GmxSeed s = table[code];
   if (s.a != GMX_SEED_COMPLEX) {
-    if (s.a <= s.b) push(s.a, s.b, GMX_NIL, GMX_NIL);
+    // (a push that does not fit is an overflow here as below: a caller that takes the interval apart position by position —
+    //  the large-capacity search, the last tier — would otherwise go on with the positions that did fit)
+    if (s.a <= s.b && !push(s.a, s.b, GMX_NIL, GMX_NIL)) ctx.fail(GMX_TASK_OVERFLOW);
     return;
   }
   const uint32_t *p = gmx_seed_entry(ix, s.b);

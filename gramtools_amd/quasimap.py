@@ -694,6 +694,15 @@ class Quasimapper:
         check(self.lib.gmx_debug_straggler_counts(self.h, out))
         return [int(x) for x in out]
 
+    COVER_COUNTS = ("general", "general_rest", "coop_rejected_general", "coop_rejected_inst", "coop_rejected_big", "mid", "overflow",
+                    "huge_cover", "huge_search", "big_mapped", "inst_mapped", "tail_retry")
+
+    def debug_cover_counts(self):
+        """The coverage ladder's queue lengths of the last batch, one by one (gmx_debug_cover_counts): a dict over COVER_COUNTS."""
+        out = (C.c_uint64 * len(self.COVER_COUNTS))()
+        check(self.lib.gmx_debug_cover_counts(self.h, out))
+        return {name: int(x) for name, x in zip(self.COVER_COUNTS, out)}
+
     # ---- test hooks: SearchStates of the HIP path (gmx.h; states as (lo, hi, [(site, allele)...], [(site, -1)...])) ----
     @staticmethod
     def _states_to_words(states):

@@ -485,6 +485,13 @@ int gmx_engine_queue_counts(gmx_engine *e, gmx_queue_counts *out);
 /* Test hook beside it: out[pass] = the tasks of the LAST batch that the extend kernel parked with work left when its iteration
  * budget ran out (GMX_EXTEND_BUDGET, GMX_EXTEND_PASSES), for its straggler pass 0, 1 and 2. All zero without a budget. */
 int gmx_debug_straggler_counts(gmx_engine *e, uint64_t out[3]);
+/* Test hook: the coverage ladder's queues of the LAST batch, one by one. out[0] general (every task the general coverage routine
+ * had to take)   [1] general_rest (what gmx_cover_one_kernel left of them)   [2] [3] [4] entries the cooperative kernel left to the
+ * one-lane instance of its queue: regular tasks, instance-searched tasks, large-capacity tasks   [5] mid (beyond the first LDS
+ * scratch)   [6] overflow (beyond the regular / large-capacity tasks' scratch)   [7] huge_cover (beyond the large scratch)
+ * [8] huge_search   [9] big_mapped   [10] inst_mapped   [11] tail_retry: work items of the heap-backed tier that did not fit a
+ * 64th of the heap and were redone by one lane with all of it. */
+int gmx_debug_cover_counts(gmx_engine *e, uint64_t out[12]);
 
 /* The i-th master-generator draws for reads_per_file (quasimap.cpp:120-141: 5000 draws per batch of
  * <= 5000 reads, one mt19937(master_seed) shared by all files). `out` receives sum(reads_per_file) seeds. */

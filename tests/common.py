@@ -72,6 +72,9 @@ def _load_emu():
     lib.hostemu_destroy.argtypes = [C.c_void_p]
     lib.hostemu_set_single_loci.argtypes = [C.c_void_p, C.c_uint32]
     lib.hostemu_set_wide.argtypes = [C.c_void_p, C.c_int]
+    lib.hostemu_set_coop.argtypes = [C.c_void_p, C.c_int]
+    lib.hostemu_set_seed_split.argtypes = [C.c_void_p, C.c_uint32]
+    lib.hostemu_capacities.argtypes = [C.POINTER(C.c_uint32)]
     lib.hostemu_n_wide.restype = C.c_uint64
     lib.hostemu_n_wide.argtypes = [C.c_void_p]
     lib.hostemu_map.restype = C.c_int
@@ -86,9 +89,18 @@ def _load_emu():
     return lib
 
 
+# hostemu_sizes [4..]: tasks the fast pass handed to the large-capacity search, tasks that needed the large scratch ([5] = regular_to_big
+# + mid_to_big), the heap-backed tier's tasks, then one count per hand-over
+HOSTEMU_COUNTS = ("overflow_tasks", "cover_overflow", "cover_huge", "lds_to_regular", "regular_to_big", "mid_to_big", "general_fast",
+                  "general_big", "coop_reject_fast", "coop_reject_big", "coop5_reject_big")
+
+
 def hostemu_map(prg, k, reads, seeds, rng_mode=0, fast_states=8, fast_arena=24, big_states=1024, big_arena=2048,
-                return_raw=False, single_loci=None, wide=False, stats=None, stage=0):
-    """Runs the device headers on the host. Returns (canonical coverage, n_overflow_tasks, rc)."""
+                return_raw=False, single_loci=None, wide=False, stats=None, stage=0, coop=False, counts=None, seed_split=0):
+    """Runs the device headers on the host. Returns (canonical coverage, (n_overflow_tasks, n_cover_overflow, n_cover_huge), rc).
+    counts (a dict): receives one count per hand-over of the coverage ladder (HOSTEMU_COUNTS); coop: also how many tasks the
+    cooperative instances would reject; seed_split: a path-less seed over more than that many positions skips the fast pass
+    (the engine's GMX_SEED_SPLIT_MAX; 0: every task starts there)."""
     lib = _load_emu()
     arr = np.ascontiguousarray(prg, dtype=np.uint32)
     err = C.create_string_buffer(512)
@@ -103,6 +115,10 @@ def hostemu_map(prg, k, reads, seeds, rng_mode=0, fast_states=8, fast_arena=24, 
         if single_loci is not None:  # loci capacity of the nested single-instance routine (gmx_cover.h)
             lib.hostemu_set_single_loci(h, single_loci)
         lib.hostemu_set_stage(stage)  # operations gmx_cover_jump stages between its check pass and the recording (gmx_cover.h)
+        if seed_split:
+            lib.hostemu_set_seed_split(h, seed_split)
+        if coop:  # the cooperative instances' reject rule, stated per task (a dry run of the routine each)
+            lib.hostemu_set_coop(h, 1)
         if wide:  # single-instance tasks through gmx_cover_single_nested_wide (the routine of gmx_cover_one_kernel)
             lib.hostemu_set_wide(h, 1)
         rc = lib.hostemu_map(h, flat.ctypes.data_as(C.POINTER(C.c_uint8)), offs.ctypes.data_as(C.POINTER(C.c_uint64)),
@@ -113,8 +129,10 @@ def hostemu_map(prg, k, reads, seeds, rng_mode=0, fast_states=8, fast_arena=24, 
             routes = np.zeros(3, dtype=np.uint64)  # single-instance tasks by routine: walk-free, jump, walk (process-wide: reset here)
             lib.hostemu_routes(routes.ctypes.data_as(C.POINTER(C.c_uint64)), 1)
             stats["routes"] = [int(x) for x in routes]
-        sizes = np.zeros(7, dtype=np.uint64)
+        sizes = np.zeros(7 + len(HOSTEMU_COUNTS) - 3, dtype=np.uint64)
         lib.hostemu_sizes(h, sizes.ctypes.data_as(C.POINTER(C.c_uint64)))
+        if counts is not None:
+            counts.update(zip(HOSTEMU_COUNTS, (int(x) for x in sizes[4:])))
         a = np.zeros(max(int(sizes[0]), 1), dtype=np.uint32)
         p = np.zeros(max(int(sizes[1]), 1), dtype=np.uint32)
         g = np.zeros(max(int(sizes[2]), 1), dtype=np.uint32)

@@ -111,15 +111,22 @@ struct Emu {
   int rng_mode = 0;
   uint32_t first_error = 0, error_task = 0;
   uint64_t n_overflow_tasks = 0, n_cover_overflow = 0, n_cover_huge = 0;
+  // one count per hand-over of the coverage ladder (hostemu_sizes [7..]): Lds -> CoverEnv, CoverEnv -> Big, Mid -> Big, tasks the
+  // general routine saw (fast pass / large-capacity search), tasks the cooperative instances 3 / 2 / 5 would reject (hostemu_set_coop)
+  uint64_t n_lds_to_regular = 0, n_regular_to_big = 0, n_mid_to_big = 0, n_general_fast = 0, n_general_big = 0, n_coop_reject_fast = 0,
+           n_coop_reject_big = 0, n_coop5_reject_big = 0;
+  uint32_t seed_split = 0;  // hostemu_set_seed_split: gmx_seed_kernel's rule (GMX_SEED_SPLIT_MAX; 0: off)
+  Emu *dry = nullptr;  // (takes the dry run's records, never read)
+  int coop = 0;  // hostemu_set_coop: state the cooperative instances' reject rule per task (costs a dry run of the routine)
   uint32_t single_loci = GMX_SINGLE_LOCI;  // hostemu_set_single_loci: force the nested single-instance routine to give up
   int wide = 0;  // hostemu_set_wide: single-instance tasks take gmx_cover_single_nested_wide first (gmx_cover_one_kernel's routine)
   uint64_t n_wide = 0;
   std::string err;
 };
 
-template <uint32_t I_, uint32_t B_, uint32_t LOC_, uint32_t H_>
+template <uint32_t I_, uint32_t B_, uint32_t LOC_, uint32_t H_, uint32_t P_ = GMX_PATH_CACHE>
 struct EmuEnvT {
-  static constexpr uint32_t I_MAX = I_, B_MAX = B_, LOC_MAX = LOC_, H_MAX = H_;
+  static constexpr uint32_t I_MAX = I_, B_MAX = B_, LOC_MAX = LOC_, H_MAX = H_, P_MAX = P_;
   static constexpr uint32_t i_max() { return I_; }
   static constexpr uint32_t b_max() { return B_; }
   static constexpr uint32_t loc_max() { return LOC_; }
@@ -212,8 +219,24 @@ struct EmuEnvDyn {
   }
 };
 
-typedef EmuEnvT<32, 8, 64, 64> EmuEnv;            // same capacities as CoverEnv / CoverEnvBig in gmx_engine.hip
-typedef EmuEnvT<1024, 32, 1024, 1024> EmuEnvBig;
+// The engine's fixed tiers (gmx_engine_cover_kernels.h), from the same statement of their capacities (gmx_cover.h)
+typedef EmuEnvT<GMX_TIER_ARGS(GMX_CAPS_LDS)> EmuEnvLds;      // CoverEnvLds
+typedef EmuEnvT<GMX_TIER_ARGS(GMX_CAPS_MID)> EmuEnvMid;      // CoverEnvMid
+typedef EmuEnvT<GMX_TIER_ARGS(GMX_CAPS_REGULAR)> EmuEnv;     // CoverEnv
+typedef EmuEnvT<GMX_TIER_ARGS(GMX_CAPS_BIG)> EmuEnvBig;      // CoverEnvBig
+// The host has no wave: the cooperative instances are mirrored as their reject rule alone (coop_rejects). An item lane's
+// scratch, and the rest of the rule as one scratch for gmx_cover_task: up to 16 items, keys and path cache of an item lane,
+// loci and hull of the class scratch.
+template <int LIST>
+struct EmuCoop {
+  typedef EmuEnvT<GMX_TIER_ARGS(GMX_CAPS_COOP_ITEM)> Item;
+  typedef EmuEnvT<GMX_COOP_UNITS, GMX_CAPS_COOP_ITEM.key_sites, GMX_CAPS_COOP_CLASS.loci, GMX_CAPS_COOP_CLASS.hull, GMX_CAPS_COOP_ITEM.path> Task;
+};
+template <>
+struct EmuCoop<5> {
+  typedef EmuEnvT<GMX_TIER_ARGS(GMX_CAPS_COOP5_ITEM)> Item;
+  typedef EmuEnvT<GMX_COOP_UNITS, GMX_CAPS_COOP5_ITEM.key_sites, GMX_CAPS_COOP5_CLASS.loci, GMX_CAPS_COOP5_CLASS.hull, GMX_CAPS_COOP5_ITEM.path> Task;
+};
 
 struct Read {
   const uint8_t *p;
@@ -331,6 +354,54 @@ void search_task(const GmxIndexView &ix, const Read &r, EmuCtx &ctx) {
   }
 }
 
+// gmx_cover_coop_kernel's reject rule for one task: more than 16 final states or units (a path-bearing or text-form state is
+// one unit, a pathless interval one per occurrence), an item that exceeds an item lane's scratch, or a drawn class that
+// exceeds the class scratch. `dry` takes the dry run's records and is never read.
+template <int LIST>
+bool coop_rejects(const GmxIndexView &ix, Emu *dry, const GmxFinalState *st, uint32_t nf, const GmxPathNode *arena, uint32_t len,
+                  uint32_t seed, int rng_mode) {
+  if (nf > GMX_COOP_UNITS) return true;
+  uint64_t units = 0;
+  for (uint32_t f = 0; f < nf; ++f)
+    units += (st[f].traversed != GMX_NIL || st[f].traversing != GMX_NIL || gmx_text_form(st[f].hi)) ? 1u : (uint64_t)(st[f].hi - st[f].lo) + 1u;
+  if (units > GMX_COOP_UNITS) return true;
+  typedef typename EmuCoop<LIST>::Item ItemEnv;
+  typedef GmxScratch<ItemEnv> SI;
+  bool over = false;
+  gmx_final_items(ix, st, nf,
+                  [&](uint32_t lo, uint32_t hi, uint32_t tvd, uint32_t tvg, uint32_t es, int32_t ea) -> bool {
+                    ItemEnv ie;  // the lane's own scratch: one item, its loci window and key
+                    ie.e = dry;
+                    ie.arena = arena;
+                    const uint32_t w[6] = {lo, hi, tvd, tvg, es, (uint32_t)ea};
+                    for (uint32_t t = 0; t < 6; ++t) ie.sset(SI::items + t, w[t]);
+                    const uint32_t nl = gmx_item_loci(ix, ie, 0, 0);
+                    if (nl != 0xFFFFFFFFu) gmx_item_key(ix, ie, 0, 0, nl);
+                    over = over || ie.status == GMX_TASK_OVERFLOW;
+                    return true;
+                  },
+                  [](uint32_t, uint32_t) {});
+  if (over) return true;
+  typename EmuCoop<LIST>::Task te;  // the drawn class against the class scratch
+  te.e = dry;
+  te.arena = arena;
+  gmx_cover_task(ix, te, st, nf, len, seed, rng_mode);
+  return te.status == GMX_TASK_OVERFLOW;
+}
+
+// One fixed tier: gmx_cover_task with that tier's scratch. -> the task's status (a log reservation that does not cover what
+// the task appended is an error)
+template <class Env>
+uint32_t cover_with(const GmxIndexView &ix, Emu *e, const GmxFinalState *st, uint32_t nf, const GmxPathNode *arena, uint32_t len,
+                    uint32_t seed) {
+  Env env;
+  env.arena = arena;
+  env.e = e;
+  gmx_cover_task(ix, env, st, nf, len, seed, e->rng_mode);
+  if (env.status == GMX_TASK_MAPPED && env.reserved != env.appended) return GMX_TASK_ERROR;
+  return env.status;
+}
+
 }  // namespace
 
 extern "C" {
@@ -350,9 +421,34 @@ void *hostemu_create(const uint32_t *prg, uint64_t n, uint32_t k, int rng_mode, 
     return nullptr;
   }
 }
-void hostemu_destroy(void *p) { delete (Emu *)p; }
+void hostemu_destroy(void *p) {
+  delete ((Emu *)p)->dry;
+  delete (Emu *)p;
+}
+void hostemu_set_seed_split(void *p, uint32_t n) { static_cast<Emu *>(p)->seed_split = n; }
+void hostemu_set_coop(void *p, int on) {
+  Emu *e = static_cast<Emu *>(p);
+  e->coop = on;
+  if (on && !e->dry) {
+    e->dry = new Emu();
+    e->dry->acc.assign(e->acc.size(), 0);
+  }
+}
+// The fixed tiers' capacities as the headers state them, five words each (GmxTierCaps): Lds, Mid, CoverEnv, Big, the
+// cooperative Item and Class of instances 3 / 2, those of instance 5; then GMX_COOP_UNITS, GMX_SINGLE_LOCI, GMX_WIDE_LOCI.
+void hostemu_capacities(uint32_t *out) {
+  const GmxTierCaps all[8] = {GMX_CAPS_LDS, GMX_CAPS_MID, GMX_CAPS_REGULAR, GMX_CAPS_BIG, GMX_CAPS_COOP_ITEM, GMX_CAPS_COOP_CLASS,
+                              GMX_CAPS_COOP5_ITEM, GMX_CAPS_COOP5_CLASS};
+  for (int t = 0; t < 8; ++t) {
+    const uint32_t w[5] = {all[t].items, all[t].key_sites, all[t].loci, all[t].hull, all[t].path};
+    for (int i = 0; i < 5; ++i) out[5 * t + i] = w[i];
+  }
+  out[40] = GMX_COOP_UNITS;
+  out[41] = GMX_SINGLE_LOCI;
+  out[42] = GMX_WIDE_LOCI;
+}
 
-// Same two-tier flow as launch_batch(): fast pass (4 states / 24 arena nodes), large-capacity pass, cover, stats.
+// Same two-tier flow as launch_batch(): fast pass, large-capacity pass, the coverage ladder, stats.
 void hostemu_set_wide(void *p, int on) { static_cast<Emu *>(p)->wide = on; }
 void hostemu_routes(uint64_t *out, int reset) {
   for (int i = 0; i < 3; ++i) {
@@ -384,7 +480,21 @@ int hostemu_map(void *p, const uint8_t *reads, const uint64_t *offsets, const ui
       Read r{reads + offsets[read], len, o == 1};
       // fast tier: the DFS loop with the kernel's capacities (stack = fast_states - 2, parked <= stack, finals <= fast_states)
       EmuDfsCtx dfs(fast_states > 2 ? fast_states - 2 : 1, fast_states > 2 ? fast_states - 2 : 1, fast_arena);
-      dfs_task(ix, r, dfs, 6, fast_states);
+      // gmx_seed_kernel: a path-less seed over more positions than the fast pass takes apart goes straight to the searches behind it
+      const GmxSeed sd = ix.seeds[kmer_code(r, len - ix.kmer_size, ix.kmer_size)];
+      bool seed_over = e->seed_split && sd.a != GMX_SEED_COMPLEX && sd.a <= sd.b && sd.b - sd.a >= e->seed_split;
+      if (e->seed_split && sd.a == GMX_SEED_COMPLEX) {  // (gmx_seed_mark_kernel: a multi-state entry with such a path-less state)
+        const uint32_t *w = ix.seed_words + ((size_t)sd.b << ix.seed_shift);
+        const uint32_t ns = *w++;
+        for (uint32_t j = 0; j < ns; ++j) {
+          seed_over = seed_over || (w[1] >= w[0] + e->seed_split && w[2] == 0 && w[3] == 0);
+          w += 4 + 2 * w[2] + w[3];
+        }
+      }
+      if (seed_over)
+        dfs.status = GMX_TASK_OVERFLOW;
+      else
+        dfs_task(ix, r, dfs, 6, fast_states);
       EmuCtx big(big_states, big_arena);
       struct View {
         const GmxFinalState *st;
@@ -409,25 +519,46 @@ int hostemu_map(void *p, const uint8_t *reads, const uint64_t *offsets, const ui
         continue;
       }
       e->stats[4]++;
-      EmuEnv env;
-      env.arena = use.arena;
-      env.e = e;
+      const bool from_big = use.st == big.st.data();  // a task of the large-capacity search
+      uint32_t cstatus = GMX_TASK_MAPPED;
       bool taken = false;
       if (e->wide && use.n == 1 && (gmx_text_form(use.st[0].hi) || use.st[0].lo == use.st[0].hi)) {
+        EmuEnv env;
+        env.arena = use.arena;
+        env.e = e;
         taken = gmx_cover_single_nested_wide(ix, env, use.st[0], len);  // false: nothing recorded, the general routine next
         if (taken) e->n_wide++;
+        if (taken) cstatus = env.status == GMX_TASK_MAPPED && env.reserved != env.appended ? GMX_TASK_ERROR : env.status;
       }
-      if (!taken) gmx_cover_task(ix, env, use.st, use.n, len, seeds[read], e->rng_mode);
-      uint32_t cstatus = env.status;
-      if (cstatus == GMX_TASK_MAPPED && env.reserved != env.appended) cstatus = GMX_TASK_ERROR;  // log reservation mismatch
-      if (cstatus == GMX_TASK_OVERFLOW) {  // nothing recorded yet: redo with the large scratch
+      if (!taken) {
+        // The ladder of gmx_engine_batch.h. An entry that exceeds a scratch has recorded nothing yet: the next tier redoes it.
+        //   fast pass:              CoverEnvLds -> CoverEnv -> CoverEnvBig -> the heap-backed tier
+        //   large-capacity search:  CoverEnvMid -> CoverEnvBig -> the heap-backed tier
+        (from_big ? e->n_general_big : e->n_general_fast)++;
+        if (e->coop) {
+          Emu &dry = *e->dry;
+          const bool rej = from_big ? coop_rejects<2>(ix, &dry, use.st, use.n, use.arena, len, seeds[read], e->rng_mode)
+                                    : coop_rejects<3>(ix, &dry, use.st, use.n, use.arena, len, seeds[read], e->rng_mode);
+          if (rej) (from_big ? e->n_coop_reject_big : e->n_coop_reject_fast)++;
+          // (instance 5 takes the same kind of task when the engine searched it one lane per instance: its smaller scratch)
+          if (from_big && coop_rejects<5>(ix, &dry, use.st, use.n, use.arena, len, seeds[read], e->rng_mode)) e->n_coop5_reject_big++;
+          dry.log.clear();
+        }
+        if (from_big) {
+          cstatus = cover_with<EmuEnvMid>(ix, e, use.st, use.n, use.arena, len, seeds[read]);
+          if (cstatus == GMX_TASK_OVERFLOW) e->n_mid_to_big++;
+        } else {
+          cstatus = cover_with<EmuEnvLds>(ix, e, use.st, use.n, use.arena, len, seeds[read]);
+          if (cstatus == GMX_TASK_OVERFLOW) {
+            e->n_lds_to_regular++;
+            cstatus = cover_with<EmuEnv>(ix, e, use.st, use.n, use.arena, len, seeds[read]);
+            if (cstatus == GMX_TASK_OVERFLOW) e->n_regular_to_big++;
+          }
+        }
+      }
+      if (cstatus == GMX_TASK_OVERFLOW) {  // the large scratch
         e->n_cover_overflow++;
-        EmuEnvBig big_env;
-        big_env.arena = use.arena;
-        big_env.e = e;
-        gmx_cover_task(ix, big_env, use.st, use.n, len, seeds[read], e->rng_mode);
-        cstatus = big_env.status;
-        if (cstatus == GMX_TASK_MAPPED && big_env.reserved != big_env.appended) cstatus = GMX_TASK_ERROR;
+        cstatus = cover_with<EmuEnvBig>(ix, e, use.st, use.n, use.arena, len, seeds[read]);
       }
       if (cstatus == GMX_TASK_OVERFLOW) {  // the last tier (gmx_tail_item): scratch sized for this task
         e->n_cover_huge++;
@@ -472,6 +603,15 @@ void hostemu_sizes(void *p, uint64_t *out) {
   out[4] = e->n_overflow_tasks;
   out[5] = e->n_cover_overflow;
   out[6] = e->n_cover_huge;
+  // one count per hand-over ([5] = [8] + [9])
+  out[7] = e->n_lds_to_regular;
+  out[8] = e->n_regular_to_big;
+  out[9] = e->n_mid_to_big;
+  out[10] = e->n_general_fast;
+  out[11] = e->n_general_big;
+  out[12] = e->n_coop_reject_fast;
+  out[13] = e->n_coop_reject_big;
+  out[14] = e->n_coop5_reject_big;
 }
 void hostemu_fetch(void *p, uint32_t *allele_sum, uint32_t *per_base, uint32_t *grouped, uint32_t *log, uint64_t *stats) {
   Emu *e = (Emu *)p;
