@@ -10,6 +10,7 @@ from .quasimap import (  # noqa: F401
     PackedReads,
     Ingest,
     bgzf_members,
+    quality_trim_length,
     PinnedArray,
     pack_reads, pack_reads_2bit,
     QuasimapperGroup,

@@ -120,6 +120,9 @@ SYMBOLS = {
     "gmx_ingest_max_compressed": (_u64, [_vp]),
     "gmx_ingest_reset": (C.c_int, [_vp]),
     "gmx_ingest_set_format": (C.c_int, [_vp, C.c_int]),
+    "gmx_ingest_set_quality_trim": (C.c_int, [_vp, C.c_uint32, C.c_uint32]),
+    "gmx_ingest_trim_stats": (C.c_int, [_vp, C.c_int, C.POINTER(_u64)]),
+    "gmx_quality_trim_length": (C.c_uint32, [_vp, C.c_uint32, C.c_uint32]),
     "gmx_ingest_set_bam_header": (C.c_int, [_vp, _u64]),
     "gmx_ingest_bam_rewalks": (_i64, [_vp]),
     "gmx_ingest_submit_bgzf": (C.c_int, [_vp, C.c_int, _vp, _u64, C.POINTER(BgzfMember), _u64, C.c_int]),

@@ -16,6 +16,7 @@
 #include "gmx_core.h"
 #include "gmx_internal.h"
 #include "gmx_link.h"
+#include "gmx_qtrim.h"
 
 static std::atomic<uint64_t> g_index_serial{1};
 struct gmx_index {
@@ -699,6 +700,11 @@ int gmx_pack_reads(const uint8_t *reads, const uint64_t *offsets, uint32_t unifo
   (void)n_pairs;
   return GMX_OK;
 } GMX_GUARD_INT("gmx_pack_reads")
+
+// ---- quality trimming: the rule of gmx_qtrim.h as the host compiles it (gram_main.cpp's reader calls the header itself) -----
+uint32_t gmx_quality_trim_length(const uint8_t *qual, uint32_t n, uint32_t min_quality) try {
+  return qual || n == 0 ? gmx_qtrim_length(qual, n, min_quality) : 0u;
+} GMX_GUARD_ZERO("gmx_quality_trim_length")
 
 // ---- reads as a 2-bit stream (gmx_map_reads_2bit_host): base j of the batch in bits 2j, 2j + 1 of the stream -------------
 uint64_t gmx_twobit_units(const uint64_t *offsets, uint32_t uniform_len, uint64_t n_reads) try {

@@ -12,6 +12,7 @@
 //                          member's text by the same wave (64 slices, GF(2) combination), compared with the trailer's.
 //   gmx_nl_count/_mark     newline positions of the chunk's text (tile counts -> scan -> positions)
 //   gmx_records_kernel     four-line records: checks '@' / '+' / equal lengths, read lengths, one length for all or not
+//   gmx_records_trim_kernel  the same with the reads' 3' ends trimmed by quality (gmx_ingest_set_quality_trim), in its place
 //   gmx_fq_pack_kernel     32 letters -> one pair of bit planes, in the layout gmx_pack_reads / the host parser produce
 //                          (include/gmx.h), unencodable reads flagged in skip[] (encode_dna_bases, common/utils.cpp:73-92)
 //   gmx_seq_lines1-3 / gmx_seq_records / gmx_seq_pack   FASTA and one-read-per-line text (gmx_ingest_set_format) in place of
@@ -36,6 +37,7 @@
 #include <vector>
 
 #include "gmx_internal.h"
+#include "gmx_qtrim.h"  // gmx_qtrim_length: the trimming rule, shared with `gram`'s host reader
 
 // The rest of this translation unit, in six parts (one TU: the kernels share the chunk's state, the launch code names the kernels):
 #include "gmx_ingest_state.h"    // ING_TRY, IngestState, IngestInflateStatus, IngestMember

@@ -26,6 +26,7 @@ struct gmx_ingest {
     uint32_t *d_bam_guess = nullptr, *d_bam_exit = nullptr, *d_bam_count = nullptr, *d_bam_flag = nullptr, *d_bam_starts = nullptr, *d_bam_blk = nullptr;
     uint8_t *d_bam_rev = nullptr;
     IngestState *d_state = nullptr, *h_state = nullptr;
+    unsigned long long *d_trim = nullptr, *h_trim = nullptr;  // gmx_ingest_set_quality_trim: the chunk's four counters (gmx_ingest_trim_stats)
     IngestMember *h_members = nullptr;  // page-locked staging of the member table
     IngestInflateStatus *d_inflate_status = nullptr;
     hipStream_t inflate_stream = nullptr;  // the slot's inflate kernel: beside the scan of the chunk before and the tail of its inflate kernel
@@ -41,6 +42,7 @@ struct gmx_ingest {
   } slot[GMX_INGEST_SLOTS];
   int last_slot = -1;  // the slot whose chunk the next one continues (-1: a file's first chunk)
   int format = GMX_INGEST_FORMAT_FASTQ;  // gmx_ingest_set_format
+  uint32_t trim_quality = 0, trim_min_length = 0;  // gmx_ingest_set_quality_trim (0: off)
   std::vector<void *> allocs;
   int check_crc = 1;
   uint32_t exp_mode = 0;
@@ -147,9 +149,10 @@ int gmx_ingest_create(int device, uint64_t max_text_bytes, gmx_ingest **out) try
         (rc = ing_alloc(g, &s.d_tiles, g->n_tiles_max + 1, false)) || (rc = ing_alloc(g, &s.d_tile_blk, g->n_tiles_max / ING_SCAN_BLOCK + 2, false)) ||
         (rc = ing_alloc(g, &s.d_off_blk, (size_t)g->cap_reads / ING_SCAN_BLOCK + 2, false)) || (rc = ing_alloc(g, &s.d_planes, max_text_bytes / 16 + 2ull * g->cap_reads + 64, false)) ||
         (rc = ing_alloc(g, &s.d_offsets, (size_t)g->cap_reads + 1, false)) || (rc = ing_alloc(g, &s.d_skip, g->cap_reads, false)) ||
-        (rc = ing_alloc(g, &s.d_state, 1, true)) || (rc = ing_alloc(g, &s.d_inflate_status, 1, true)))
+        (rc = ing_alloc(g, &s.d_state, 1, true)) || (rc = ing_alloc(g, &s.d_inflate_status, 1, true)) || (rc = ing_alloc(g, &s.d_trim, 4, true)))
       return fail(rc);
     if (hipHostMalloc(reinterpret_cast<void **>(&s.h_state), sizeof(IngestState), hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void **>(&s.h_trim), 4 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess ||
         hipHostMalloc(reinterpret_cast<void **>(&s.h_members), (size_t)g->cap_members * sizeof(IngestMember), hipHostMallocDefault) != hipSuccess ||
         hipEventCreateWithFlags(&s.copied, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&s.done, hipEventDisableTiming | hipEventBlockingSync) != hipSuccess ||
@@ -178,6 +181,7 @@ void gmx_ingest_destroy(gmx_ingest *g) try {
   }
   for (auto &s : g->slot) {
     if (s.h_state) (void)hipHostFree(s.h_state);
+    if (s.h_trim) (void)hipHostFree(s.h_trim);
     if (s.h_members) (void)hipHostFree(s.h_members);
     if (s.copied) (void)hipEventDestroy(s.copied);
     if (s.done) (void)hipEventDestroy(s.done);
@@ -212,6 +216,10 @@ int gmx_ingest_set_format(gmx_ingest *g, int format) try {
       gmx_set_error("gmx_ingest_set_format: a slot's chunk is in flight (the format is set between files)");
       return GMX_EINVAL;
     }
+  if (format == GMX_INGEST_FORMAT_BAM && g->trim_quality) {
+    gmx_set_error("gmx_ingest_set_format: BAM records are not trimmed on the device (gmx_ingest_set_quality_trim is on: switch it off, or read the file on the host)");
+    return GMX_EINVAL;
+  }
   int rc;
   if (format == GMX_INGEST_FORMAT_BAM && !g->slot[GMX_INGEST_SLOTS - 1].d_bam_rev) {  // the tile tables, once
     uint64_t tile = 4096;
@@ -245,6 +253,34 @@ int gmx_ingest_set_format(gmx_ingest *g, int format) try {
   g->bam_header_left = 0;
   return GMX_OK;
 } GMX_GUARD_INT("gmx_ingest_set_format")
+
+int gmx_ingest_set_quality_trim(gmx_ingest *g, uint32_t min_quality, uint32_t min_length) try {
+  if (!g || min_quality > GMX_QTRIM_MAX_QUALITY || (min_quality && min_length < 1)) {
+    gmx_set_error("gmx_ingest_set_quality_trim: null ingest, min_quality above 93, or min_length 0 (min_quality 0 switches trimming off)");
+    return GMX_EINVAL;
+  }
+  for (const auto &s : g->slot)
+    if (s.in_flight || s.deferred) {
+      gmx_set_error("gmx_ingest_set_quality_trim: a slot's chunk is in flight (trimming is set between files)");
+      return GMX_EINVAL;
+    }
+  if (min_quality && g->format == GMX_INGEST_FORMAT_BAM) {
+    gmx_set_error("gmx_ingest_set_quality_trim: BAM records are not trimmed on the device (read the file on the host)");
+    return GMX_EINVAL;
+  }
+  g->trim_quality = min_quality;
+  g->trim_min_length = min_quality ? min_length : 0;
+  return GMX_OK;
+} GMX_GUARD_INT("gmx_ingest_set_quality_trim")
+
+int gmx_ingest_trim_stats(gmx_ingest *g, int slot, uint64_t out[4]) try {
+  if (!g || slot < 0 || slot >= GMX_INGEST_SLOTS || !out || g->slot[slot].in_flight || g->slot[slot].deferred) {
+    gmx_set_error("gmx_ingest_trim_stats: null argument, bad slot, or the slot's chunk is still in flight (after its gmx_ingest_wait)");
+    return GMX_EINVAL;
+  }
+  for (int i = 0; i < 4; ++i) out[i] = g->slot[slot].h_trim[i];
+  return GMX_OK;
+} GMX_GUARD_INT("gmx_ingest_trim_stats")
 
 int gmx_ingest_set_bam_header(gmx_ingest *g, uint64_t header_bytes) try {
   if (!g || g->format != GMX_INGEST_FORMAT_BAM) {
@@ -342,6 +378,10 @@ static int ing_enqueue_tail(gmx_ingest *g, int si, const IngChunk &c) {
                        s.d_rec_len, s.d_offsets, s.d_planes, s.d_skip);
   ING_TRY(hipGetLastError());
   ING_TRY(hipMemcpyAsync(s.h_state, s.d_state, sizeof(IngestState), hipMemcpyDeviceToHost, g->stream));
+  if (g->trim_quality && g->format == GMX_INGEST_FORMAT_FASTQ)  // (the only format with qualities to trim by: the others' counters stay zero)
+    ING_TRY(hipMemcpyAsync(s.h_trim, s.d_trim, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, g->stream));
+  else
+    memset(s.h_trim, 0, 4 * sizeof(unsigned long long));  // (nothing of the slot is in flight: ing_begin)
   ING_TRY(hipEventRecord(s.done, g->stream));
   s.in_flight = true;
   s.deferred = false;
@@ -409,7 +449,11 @@ static int ing_enqueue_scan(gmx_ingest *g, int si, const IngChunk &c) {
   hipLaunchKernelGGL(gmx_tile_scan2_kernel, dim3(1), dim3(64), 0, g->stream, s.d_tile_blk, n_tile_blk, s.d_state, g->cap_lines);
   hipLaunchKernelGGL(gmx_nl_mark_kernel, dim3(n_tiles), dim3(256), 0, g->stream, s.d_text, s.d_state, s.d_tiles, s.d_tile_blk, s.d_line_end, g->cap_lines);
   const uint32_t fmt = (uint32_t)g->format;
-  if (fmt == GMX_INGEST_FORMAT_FASTQ) {
+  if (fmt == GMX_INGEST_FORMAT_FASTQ && g->trim_quality) {
+    ING_TRY(hipMemsetAsync(s.d_trim, 0, 4 * sizeof(unsigned long long), g->stream));
+    hipLaunchKernelGGL(gmx_records_trim_kernel, dim3(2048), dim3(256), 0, g->stream, (const uint8_t *)s.d_text, s.d_state, (const uint32_t *)s.d_line_end, s.d_rec_start,
+                       s.d_rec_len, s.d_skip, g->cap_reads, g->trim_quality, g->trim_min_length, s.d_trim);
+  } else if (fmt == GMX_INGEST_FORMAT_FASTQ) {
     hipLaunchKernelGGL(gmx_records_kernel, dim3(2048), dim3(256), 0, g->stream, s.d_text, s.d_state, s.d_line_end, s.d_rec_start, s.d_rec_len, s.d_skip, g->cap_reads);
   } else {  // (the chunk's line count is on the device: blocks beyond it leave at once)
     const uint32_t n_line_blk = (uint32_t)(((uint64_t)g->cap_lines + 1 + ING_SCAN_BLOCK - 1) / ING_SCAN_BLOCK);

@@ -159,8 +159,17 @@ __global__ void __launch_bounds__(256) gmx_nl_mark_kernel(const uint8_t *text, c
 
 // One thread per record (grid-stride). Line i of the chunk ends at line_end[i]; a last line without '\n' ends at the text's
 // end when the chunk is the file's last.
-__global__ void __launch_bounds__(256) gmx_records_kernel(const uint8_t *text, IngestState *st, const uint32_t *line_end, uint32_t *rec_start,
-                                                          uint32_t *rec_len, uint8_t *skip, uint32_t cap_reads) {
+// TRIM (gmx_ingest_set_quality_trim): the lane runs gmx_qtrim_length over its record's quality line, and the
+// trimmed length t takes the read's place in everything downstream: rec_len, the min / max / sum reduction (hence uniform_len,
+// the offsets, the planes). t < min_length sets the read's skip flag here (the pack kernel adds the letters' verdict on [0, t)).
+// The malformed-record test stays on the lengths as they lie in the text. trim[4]: reads shortened, bases removed, reads
+// skipped for t < min_length, bases before trimming. Two kernels around this one body, so that an ingest without trimming
+// launches the code object it always did (gmx_records_kernel: no argument, no branch added).
+template <bool TRIM>
+__device__ __forceinline__ void ing_records(const uint8_t *text, IngestState *st, const uint32_t *line_end, uint32_t *rec_start, uint32_t *rec_len, uint8_t *skip,
+                                            uint32_t cap_reads, uint32_t first, uint32_t stride, uint32_t min_quality, uint32_t min_length, unsigned long long *trim) {
+  // (first, stride: the grid-stride loop's, worked out by the kernels themselves — the block and grid sizes are folded into loads of
+  //  the dispatch packet only where a kernel's own text asks for them, and gmx_records_kernel is to stay the code it was)
   if (st->flags & GMX_INGEST_TOO_MANY_LINES) return;
   const uint32_t lo = st->text_start, hi = lo + st->text_len, n_nl = st->n_lines;
   const uint32_t last_nl_end = n_nl ? line_end[n_nl - 1] + 1u : lo;
@@ -176,7 +185,10 @@ __global__ void __launch_bounds__(256) gmx_records_kernel(const uint8_t *text, I
   uint32_t mn = 0xFFFFFFFFu, mx = 0;
   unsigned long long bases = 0;
   bool bad = false;
-  for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n_reads; r += gridDim.x * blockDim.x) {
+  [[maybe_unused]] unsigned long long bases_in = 0, removed = 0;
+  [[maybe_unused]] uint32_t shortened = 0, too_short = 0;
+  [[maybe_unused]] bool any_short = false;
+  for (uint32_t r = first; r < n_reads; r += stride) {
     const uint32_t s1 = r ? line_end[4u * r - 1u] + 1u : lo;
     const uint32_t e1 = le(4u * r), e2 = le(4u * r + 1u), e3 = le(4u * r + 2u), e4 = le(4u * r + 3u);
     const uint32_t s2 = e1 + 1u, s3 = e2 + 1u, s4 = e3 + 1u;
@@ -185,8 +197,23 @@ __global__ void __launch_bounds__(256) gmx_records_kernel(const uint8_t *text, I
     if (nq && text[s4 + nq - 1u] == '\r') --nq;
     if (text[s1] != '@' || s3 >= hi || text[s3] != '+' || nq != n || n == 0) bad = true;
     rec_start[r] = s2;
+    if constexpr (TRIM) {
+      if (nq == n && n) {  // (a malformed record is reported below: its reads are never used)
+        const uint32_t t = gmx_qtrim_length(text + s4, n, min_quality);
+        bases_in += n;
+        if (t < n) {
+          ++shortened;
+          removed += n - t;
+        }
+        if (t < min_length) {
+          ++too_short;
+          any_short = true;
+        }
+        n = t;
+      }
+    }
     rec_len[r] = n;
-    skip[r] = 0;
+    skip[r] = TRIM && n < min_length ? 1 : 0;
     mn = min(mn, n);
     mx = max(mx, n);
     bases += n;
@@ -218,6 +245,31 @@ __global__ void __launch_bounds__(256) gmx_records_kernel(const uint8_t *text, I
     if (bases) atomicAdd(&st->n_bases, bases);
     if (any_bad) atomicOr(&st->flags, GMX_INGEST_BAD_RECORD);
   }
+  if constexpr (TRIM) {
+    for (int off = 32; off > 0; off >>= 1) {
+      shortened += __shfl_down(shortened, off);
+      too_short += __shfl_down(too_short, off);
+      removed += __shfl_down(removed, off);
+      bases_in += __shfl_down(bases_in, off);
+    }
+    const unsigned long long some_short = __ballot(any_short);
+    if ((threadIdx.x & 63u) == 0) {
+      if (shortened) atomicAdd(&trim[0], (unsigned long long)shortened);
+      if (removed) atomicAdd(&trim[1], removed);
+      if (too_short) atomicAdd(&trim[2], (unsigned long long)too_short);
+      if (bases_in) atomicAdd(&trim[3], bases_in);
+      if (some_short) st->any_skip = 1;
+    }
+  }
+}
+__global__ void __launch_bounds__(256) gmx_records_kernel(const uint8_t *text, IngestState *st, const uint32_t *line_end, uint32_t *rec_start,
+                                                          uint32_t *rec_len, uint8_t *skip, uint32_t cap_reads) {
+  ing_records<false>(text, st, line_end, rec_start, rec_len, skip, cap_reads, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, 0u, 0u, nullptr);
+}
+__global__ void __launch_bounds__(256) gmx_records_trim_kernel(const uint8_t *text, IngestState *st, const uint32_t *line_end, uint32_t *rec_start,
+                                                               uint32_t *rec_len, uint8_t *skip, uint32_t cap_reads, uint32_t min_quality, uint32_t min_length,
+                                                               unsigned long long *trim) {
+  ing_records<true>(text, st, line_end, rec_start, rec_len, skip, cap_reads, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, min_quality, min_length, trim);
 }
 // one length for all reads? -> layout of the planes; reads of different lengths: their base offsets (one block)
 __global__ void __launch_bounds__(64) gmx_layout_kernel(IngestState *st, const IngestInflateStatus *inf) {

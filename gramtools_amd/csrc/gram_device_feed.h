@@ -86,6 +86,7 @@ static bool device_feeds_ready(const int *devs, size_t n, uint64_t want_text, ui
     if (!df.ing || (need_compressed && gmx_ingest_max_compressed(df.ing) < need_compressed)) return false;
     GMX_CHECK(gmx_ingest_reset(df.ing));
     GMX_CHECK(gmx_ingest_set_format(df.ing, g_reads_format));
+    if (g_trim_quality) GMX_CHECK(gmx_ingest_set_quality_trim(df.ing, g_trim_quality, g_trim_min_length));  // --trim_quality (BAM never comes here with it)
   }
   return true;
 }
@@ -124,6 +125,7 @@ static bool plain_fastq_on_device(int max_threads, size_t n_engines) {
   // FASTA / one read per line: no parallel host parser exists for them (parse_fastq_file declines), the alternative is the
   // general reader on ONE thread: the device route at every thread count
   if (g_reads_format != GMX_INGEST_FORMAT_FASTQ) return true;
+  if (g_trim_quality) return true;  // --trim_quality: the parallel host parser never sees the quality line, the record scan trims
   if (const char *e = getenv("GMX_DEVICE_FASTQ")) return atoi(e) != 0;
   (void)n_engines;  // (several engines: the same rule — the chunks are then dealt over the engines' ingests, ingest_text_file_dealt; measured
                     //  only with several engines on ONE GPU, tools/feed_x8.py, where it has nothing to gain)

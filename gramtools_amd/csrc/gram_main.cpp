@@ -44,6 +44,7 @@
 
 #include "../../include/gmx.h"
 #include "gmx_gzsource.h"
+#include "gmx_qtrim.h"  // gmx_qtrim_length: the trimming rule, shared with the device's record scan
 
 namespace {
 
@@ -120,7 +121,18 @@ const char *kGenotypeHelp =
     "                              {\"span\":D,\"links\":[[s,t,[[row]...]],...]}: one entry per pair of sites s < t with a non-zero\n"
     "                              count, ascending, rows by the allele at s, columns by the allele at t (0-based, the order of\n"
     "                              allele_sum_coverage) — and genotype_dir/site_links.json: span, sites, linkable_sites,\n"
-    "                              pairs_with_count, count. The calls do not change\n";
+    "                              pairs_with_count, count. The calls do not change\n"
+    "  --trim_quality arg          trim low-quality read ends before mapping (engine extension): Q in 1..93. Every read's 3' end is\n"
+    "                              cut by the running-sum rule of `bwa aln -q` and cutadapt `-q` over its Phred+33 qualities (walk\n"
+    "                              back from the last base adding Q - q; cut where the sum peaked, stop when it turns negative),\n"
+    "                              on the GPU for FASTQ (plain, gzip, BGZF), in the host reader for BAM and wherever that reader\n"
+    "                              takes a file. Only the bases kept are judged: an N in the part cut off does not skip the read.\n"
+    "                              FASTA and one-read-per-line files have no qualities and are not changed. A BAM record without\n"
+    "                              qualities (0xFF) counts as quality 0 throughout and trims to nothing. read_stats.json is computed\n"
+    "                              on the reads as they lie in the file. Writes genotype_dir/read_trim.json: min_quality,\n"
+    "                              min_length, reads, reads_trimmed, bases_in, bases_removed, reads_too_short\n"
+    "  --min_read_length arg       with --trim_quality: a read trimmed to fewer than M >= 1 bases is skipped (it keeps its place\n"
+    "                              and its seed, and counts as skipped). Default: --kmer_size\n";
 
 [[noreturn]] void die(const std::string &msg, int code = 1) {
   std::cout << msg << std::endl;
@@ -1046,6 +1058,12 @@ bool parse_fastq_file(const std::string &path, int threads, Sink sink) {
 // the file is compressed (BGZF and plain gzip alike). The device chain scans all three (gmx_ingest_set_format); every ingest_*
 // function below sets g_reads_format on the ingests it uses, so the caller sets it once per file.
 static int g_reads_format = GMX_INGEST_FORMAT_FASTQ;
+// --trim_quality Q / --min_read_length M (0: off): every ingest is set to them before each file (device_feeds_ready), the general
+// host reader's records are cut by them (trim_record)
+static uint32_t g_trim_quality = 0, g_trim_min_length = 0;
+struct TrimTotals {  // G/read_trim.json: the device chunks' counters (gmx_ingest_trim_stats) plus the reads the host reader delivered
+  uint64_t reads_trimmed = 0, bases_removed = 0, reads_too_short = 0, bases_in = 0;
+};
 static int detect_reads_format(const std::string &path) {
   gzFile gz = gzopen(path.c_str(), "rb");
   if (!gz) return GMX_INGEST_FORMAT_FASTQ;
@@ -1064,6 +1082,24 @@ static const char *reads_format_scanner() {
 }
 
 #include "gram_device_feed.h"  // the device feed: reads files decoded, scanned and packed on the GPU
+
+// A record of the general reader cut as the device's record scan cuts it: seq and qual keep bases [0, t). false: t < min_length,
+// the read is to be skipped. A record without qualities (FASTA, one read per line) is untouched.
+static bool trim_record(SeqRecord &rec, TrimTotals &tot) {
+  if (rec.qual.empty() || rec.qual.size() != rec.seq.size()) return true;
+  const uint32_t n = (uint32_t)rec.seq.size();
+  const uint32_t t = gmx_qtrim_length(reinterpret_cast<const uint8_t *>(rec.qual.data()), n, g_trim_quality);
+  tot.bases_in += n;
+  if (t < n) {
+    ++tot.reads_trimmed;
+    tot.bases_removed += n - t;
+    rec.seq.resize(t);
+    rec.qual.resize(t);
+  }
+  if (t >= g_trim_min_length) return true;
+  ++tot.reads_too_short;
+  return false;
+}
 
 struct ReadStats {  // include/genotype/read_stats.hpp
   double mean_cov_depth = -1, variance_cov_depth = -1;
@@ -1465,6 +1501,19 @@ int run_genotype(const Args &a) {
     if (v.size() != 1 || v[0] < '1' || v[0] > '7') die("--site_links takes a span of 1 to 7 sites (got '" + v + "')");
     site_links = v[0] - '0';
   }
+  // --trim_quality Q [--min_read_length M]: the reads' 3' ends trimmed by quality before they are packed
+  auto whole_number = [&](const char *flag, unsigned long long lo, unsigned long long hi, const std::string &range) {
+    const std::string v = a.one(flag);
+    const bool digits = !v.empty() && v.size() <= 10 && v.find_first_not_of("0123456789") == std::string::npos;
+    const unsigned long long n = digits ? std::stoull(v) : 0ull;
+    if (!digits || n < lo || n > hi) die(std::string("--") + flag + " takes a whole number " + range + " (got '" + v + "')");
+    return (uint32_t)n;
+  };
+  if (a.has("min_read_length") && !a.has("trim_quality")) die("--min_read_length is only allowed together with --trim_quality");
+  if (a.has("trim_quality")) {
+    g_trim_quality = whole_number("trim_quality", 1, GMX_QTRIM_MAX_QUALITY, "from 1 to 93");
+    g_trim_min_length = a.has("min_read_length") ? whole_number("min_read_length", 1, 0xFFFFFFFFull, ">= 1") : std::max<uint32_t>(kmer_size, 1);
+  }
   for (auto const &smp : samples) {
     mkdirs(join(smp.run_dir, "coverage"));
     mkdirs(join(smp.run_dir, "genotype"));
@@ -1645,6 +1694,7 @@ int run_genotype(const Args &a) {
   }
   ReadStats rs;
   compute_base_error_rate(reads_paths[0], rs);  // genotype.cpp:32-34
+  TrimTotals trim_totals;  // --trim_quality: this sample's
   phase("base error rate of the first 10 000 reads");
   if (sample_i > 0) {  // the accumulators and read counters of the sample before
     for (int d = 0; d < gmx_group_size(grp); ++d) GMX_CHECK(gmx_engine_reset(gmx_group_engine(grp, d)));
@@ -1681,7 +1731,8 @@ int run_genotype(const Args &a) {
     const int path_format = detect_reads_format(path);
     const bool is_bam = path_format == GMX_INGEST_FORMAT_BAM;
     // BAM: the device route at every --max_threads with one engine; several engines: the host reader into the group feed
-    if (!getenv("GMX_HOST_GZ") && !(is_bam && devices.size() > 1)) {
+    // --trim_quality: BAM records are trimmed by the host reader (their 3' end is the front of a reverse-strand record's nibbles)
+    if (!getenv("GMX_HOST_GZ") && !(is_bam && (devices.size() > 1 || g_trim_quality))) {
       g_reads_format = path_format;  // FASTA, one read per line and BAM take the same device routes (gmx_ingest_set_format)
       static std::vector<std::unique_ptr<HostBuf<uint32_t>>> dev_seeds;  // per engine and slot
       while (dev_seeds.size() < 3 * devices.size()) dev_seeds.emplace_back(new HostBuf<uint32_t>());
@@ -1691,6 +1742,14 @@ int run_genotype(const Args &a) {
       auto map_chunk = [&](const gmx_ingest_result &res, size_t k, int slot) {  // engine k's ingest holds the chunk's reads in its HBM
         const uint64_t n = res.n_reads;
         if (n == 0) return;
+        if (g_trim_quality) {  // (only chunks that are handed on come here: what the host reader re-reads after a take-over it counts itself)
+          uint64_t t4[4];
+          GMX_CHECK(gmx_ingest_trim_stats(device_feed(k).ing, slot, t4));
+          trim_totals.reads_trimmed += t4[0];
+          trim_totals.bases_removed += t4[1];
+          trim_totals.reads_too_short += t4[2];
+          trim_totals.bases_in += t4[3];
+        }
         gmx_engine *ek = gmx_group_engine(grp, (int)k);
         HostBuf<uint32_t> &sd = *dev_seeds[3 * k + (size_t)slot];
         // The kernels read the few seeds they need in place: the buffer a slot used three chunks ago must be done with. One ingest,
@@ -1767,12 +1826,13 @@ int run_genotype(const Args &a) {
       }
       total_reads += n;
     };
-    if (!is_bam && parse_fastq_file(path, max_threads, sink)) {
+    // (--trim_quality: the parallel parser never sees the quality line — the general reader below takes every host route)
+    if (!is_bam && !g_trim_quality && parse_fastq_file(path, max_threads, sink)) {
       seed_stream.base = file_base + (in_file + kBatch - 1) / kBatch * kBatch;
       continue;
     }
     // (FASTA / one read per line: the general reader below is the one that takes over, and skips what was mapped)
-    if (skip_reads && g_reads_format == GMX_INGEST_FORMAT_FASTQ) die("gram: " + path + ": the device-side decoder delivered reads of a file the host readers cannot parse");
+    if (skip_reads && g_reads_format == GMX_INGEST_FORMAT_FASTQ && !g_trim_quality) die("gram: " + path + ": the device-side decoder delivered reads of a file the host readers cannot parse");
     // (the general reader below draws from `master`: bring it to where the stream stands)
     master.seed(seed);
     master.discard(seed_stream.base);
@@ -1803,6 +1863,7 @@ int run_genotype(const Args &a) {
         total_reads++;
         continue;
       }
+      if (g_trim_quality && !trim_record(rec, trim_totals)) rec.seq.clear();  // too short: handed over empty, as an unencodable read is
       encode_read(rec.seq, bases);  // an unencodable read stays as an empty read: counted as skipped, keeps its seed
       offsets.push_back(bases.size());
       seeds.push_back(batch_seeds[in_batch]);
@@ -1945,6 +2006,14 @@ int run_genotype(const Args &a) {
   if (outcome_log.on) {
     outcome_bytes.resize(std::max<uint64_t>(total_reads, 1));
     gather_read_log(outcome_log, total_reads, gmx_group_fetch_outcomes, gmx_engine_fetch_outcomes, outcome_bytes.data(), 1);
+  }
+  if (g_trim_quality) {  // G/read_trim.json
+    const std::string path = join(run_dir, "read_trim.json");
+    std::ofstream o(path);
+    o << "{\"min_quality\":" << g_trim_quality << ",\"min_length\":" << g_trim_min_length << ",\"reads\":" << total_reads
+      << ",\"reads_trimmed\":" << trim_totals.reads_trimmed << ",\"bases_in\":" << trim_totals.bases_in << ",\"bases_removed\":" << trim_totals.bases_removed
+      << ",\"reads_too_short\":" << trim_totals.reads_too_short << "}\n";
+    close_checked(o, path);
   }
   if (max_candidates) {  // G/read_filter.json
     uint64_t mapped = 0, left_out = 0;

@@ -862,6 +862,13 @@ def bgzf_members(data) -> list:
     return out
 
 
+def quality_trim_length(qual_bytes, min_quality: int) -> int:
+    """Bases a read keeps when its 3' end is trimmed by quality (gmx_quality_trim_length: the host's compilation of the rule the
+    device's record scan applies): Phred+33 bytes, the running sum of ``bwa aln -q`` / cutadapt ``-q``."""
+    buf = np.frombuffer(bytes(qual_bytes), dtype=np.uint8)
+    return int(_lib.load().gmx_quality_trim_length(buf.ctypes.data if buf.size else None, buf.size, min_quality))
+
+
 class Ingest:
     """Reads files decoded on the device (include/gmx.h, gmx_ingest_*): BGZF members inflated, records (four-line FASTQ; FASTA, one read per
     line or BAM after ``set_format``, BAM with ``set_bam_header`` after every ``reset``) found and packed into bit planes by HIP kernels; three slots (0, 1, 2) taken in turn. ``submit_bgzf`` / ``submit_text`` / ``submit_gzip`` enqueue a chunk, ``wait`` returns
@@ -886,6 +893,18 @@ class Ingest:
     def set_format(self, fmt: int):
         """What the chunks submitted from here on hold (between files): GMX_INGEST_FORMAT_FASTQ (the default), _FASTA, _LINES or _BAM."""
         check(self.lib.gmx_ingest_set_format(self.h, fmt))
+
+    def set_quality_trim(self, min_quality: int, min_length: int = 1):
+        """Trim the reads' 3' ends by quality (gmx_ingest_set_quality_trim; between files): the running-sum rule of ``quality_trim_length``
+        at threshold min_quality (1..93; 0 switches it off), a read left with fewer than min_length bases gets its skip flag. Four-line
+        FASTQ only: FASTA and LINES accept it and are not changed, BAM refuses it."""
+        check(self.lib.gmx_ingest_set_quality_trim(self.h, min_quality, min_length))
+
+    def trim_stats(self, slot: int):
+        """After ``wait(slot)``: (reads shortened, bases removed, reads skipped as too short, bases before trimming) of the slot's chunk."""
+        out = (C.c_uint64 * 4)()
+        check(self.lib.gmx_ingest_trim_stats(self.h, slot, out))
+        return tuple(int(v) for v in out)
 
     def set_bam_header(self, header_bytes: int):
         """GMX_INGEST_FORMAT_BAM, after ``reset`` in front of a file's first chunk: the first header_bytes bytes of the file's text

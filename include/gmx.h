@@ -295,6 +295,25 @@ int gmx_ingest_reset(gmx_ingest *g); /* the next chunk is a file's first: nothin
 #define GMX_INGEST_FORMAT_LINES 2
 #define GMX_INGEST_FORMAT_BAM 3
 int gmx_ingest_set_format(gmx_ingest *g, int format);
+/* Quality trimming of the reads' 3' ends, for every chunk submitted afterwards through any of the submit calls,
+ * until set again; called between files like gmx_ingest_set_format (GMX_EINVAL while a slot's chunk is in flight). The rule is the
+ * running sum of `bwa aln -q` and cutadapt `-q` over Phred+33 qualities q_i = max(byte_i - 33, 0) of a read of n bases:
+ *     s = 0, best = 0, t = n;  for i = n - 1 down to 0: s += min_quality - q_i; s < 0: stop; s > best: best = s, t = i
+ * (a tie keeps the longer read). The read becomes its bases [0, t): that is its length in n_bases, uniform_len, d_offsets and the
+ * planes, and only those letters decide its skip flag — an N in the part trimmed off does not. A read with t < min_length keeps
+ * its place with its skip flag set (any_skip too): the engine counts it as skipped. A chunk whose reads all trim to 0 comes as
+ * FASTA reads of length 0 do (uniform_len == 0, d_offsets, n_pairs == n_reads). The malformed-record test looks at the lengths as
+ * they lie in the text. min_quality 0 switches trimming off (min_length is ignored) and the ingest launches the kernels it
+ * launched before; else 1 <= min_quality <= 93 and min_length >= 1, or GMX_EINVAL. FASTA and LINES carry no qualities: the
+ * setting is accepted and does nothing. BAM records are not trimmed on the device: GMX_EINVAL for a non-zero min_quality in
+ * GMX_INGEST_FORMAT_BAM, and for gmx_ingest_set_format(BAM) while trimming is on.
+ * gmx_ingest_trim_stats, after the slot's gmx_ingest_wait: the chunk's reads shortened, bases removed, reads skipped for
+ * t < min_length, bases before trimming (all zero with trimming off, and for FASTA / LINES). */
+int gmx_ingest_set_quality_trim(gmx_ingest *g, uint32_t min_quality, uint32_t min_length);
+int gmx_ingest_trim_stats(gmx_ingest *g, int slot, uint64_t out[4]);
+/* the rule itself on the host (what `gram`'s host reader applies; the device's record scan compiles the same text): t for the
+ * n quality bytes at qual. min_quality 0 gives n. */
+uint32_t gmx_quality_trim_length(const uint8_t *qual, uint32_t n, uint32_t min_quality);
 /* BAM (GMX_INGEST_FORMAT_BAM): the text — a BGZF file's inflated bytes through gmx_ingest_submit_bgzf, or those bytes themselves
  * through gmx_ingest_submit_text, cut anywhere — is a header and then records, all integers little-endian:
  *   header  "BAM\1", l_text:i32, text[l_text], n_ref:i32, n_ref times { l_name:i32, name[l_name], l_ref:i32 }
