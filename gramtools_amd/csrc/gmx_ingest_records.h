@@ -230,7 +230,8 @@ __device__ __forceinline__ void ing_records(const uint8_t *text, IngestState *st
     if (n_reads == 0) {
       st->consumed = lo;
       st->tail_len = hi - lo;
-      if (st->final_chunk && hi != lo) atomicOr(&st->flags, GMX_INGEST_BAD_RECORD);  // fewer than four lines at the end of the file
+      // fewer than four lines at the end of the file (more records than there is room for are well-formed: TOO_MANY_LINES alone)
+      if (st->final_chunk && hi != lo && !too_many) atomicOr(&st->flags, GMX_INGEST_BAD_RECORD);
     }
   }
   for (int off = 32; off > 0; off >>= 1) {

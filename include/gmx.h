@@ -253,7 +253,8 @@ typedef struct {
                                        * header. Every format: a record of more than 1 MB cut by a chunk's end */
 #define GMX_INGEST_BAD_MEMBER 2u      /* a member's deflate data could not be decoded */
 #define GMX_INGEST_BAD_CRC 4u         /* a member's text does not match its trailer */
-#define GMX_INGEST_TOO_MANY_LINES 8u  /* more lines / records than the ingest has room for (lines of a few bytes; BAM: records without bases) */
+#define GMX_INGEST_TOO_MANY_LINES 8u  /* more lines / records than the ingest has room for (lines of a few bytes; BAM: records without bases).
+                                       * Well-formed text that is only too dense sets this bit alone, in a file's last chunk too; n_reads is 0 */
 /* plain gzip only (gmx_ingest_submit_gzip): */
 #define GMX_INGEST_GZ_UNREPAIRED 16u   /* a piece whose speculative start did not line up could not be decoded from its predecessor's end */
 #define GMX_INGEST_GZ_LOOKAHEAD 32u    /* the chunk's last block does not end inside the look-ahead bytes given */
